@@ -10,16 +10,26 @@ N, adagrad update, per-step objective value and tail-quarter history rows.
 Draws come from the in-kernel Philox generator; everything is resident in HBM
 before timing.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--legs all|none|cfg3_256,...]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+  python bench.py --full [--legs all|none|cfg3_256,...] [--no-cpu-baseline] ...
   torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU)
+
+A plain run does only what the headline figure needs: set up, W warm-up steps,
+K timed steps, the result line.  --dump-outputs DIR then writes what the timed
+path returned after its last step (DeviceRun.result(): lam, vals, smooth and
+the tail-quarter history rows, float64 .npy files; a history above 32 MB is
+cut to a fixed, seeded sample of its rows, named in hist_rows.npy).  Inputs
+(init, Philox seed and stream) are fixed, so two builds compare file by file.
+Everything else -- the other configs' legs, the CPU baselines, the k-hat match
+and the measured roofline peaks -- runs only with --full.
 
 Multi-GPU: independent optimisation restarts (one per rank, distinct Philox
 streams) with no data-path collective -> weak scaling; an RCCL all_gather of
 the per-restart summaries closes the run.  The config-5 leg
 shards 64 restarts over the ranks (viabel_amd.restarts) the same way.
 
-After the headline, shorter legs put the other BASELINE.json configs on the
-same line ("configs"): config 3 at N = 256, configs 1, 2, 4 and 5, and the
+With --full, after the headline, shorter legs put the other BASELINE.json
+configs on the same line ("configs"): config 3 at N = 256, configs 1, 2, 4 and 5, and the
 PSIS k-hat match (device psislw vs the CPU restatement on a 1e6 log-weight
 vector).  The CPU baselines (median of 5 runs, one core, plus
 an all-core leg; host CPU model and core counts) run on rank 0 at N = 1 only.
@@ -760,17 +770,50 @@ def leg_khat(cpu):
     return out
 
 
+DUMP_HIST_BYTES = 32 << 20     # history rows above this are written as a sample
+
+
+def dump_outputs(out_dir, lam, hist, vals, smooth):
+    """The timed path's results after its last step (DeviceRun.result()) as
+    float64 .npy files: lam, vals, smooth whole; hist whole, or -- above
+    DUMP_HIST_BYTES -- a fixed sample of its rows (seeded choice plus the last
+    row, ascending), whose row numbers go to hist_rows.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n_hist = hist.shape[1]
+    rows = np.arange(n_hist)
+    keep = max(1, DUMP_HIST_BYTES // (hist.shape[0] * hist.shape[2] * hist.itemsize))
+    if n_hist > keep:
+        pick = np.random.RandomState(0).choice(n_hist - 1, keep - 1, replace=False)
+        rows = np.sort(np.append(pick, n_hist - 1))
+    out = {'lam': lam, 'vals': vals, 'smooth': smooth, 'hist': hist[:, rows],
+           'hist_rows': rows.astype(np.float64)}
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=2000)
     ap.add_argument('--warmup', type=int, default=100)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the other configs\' legs, the CPU baselines, the k-hat '
+                         'match and the peak probes (a plain run times the headline only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the arrays the timed path returned after its last step as '
+                         'DIR/<name>.npy (float64; at most 64 MB in all)')
+    ap.add_argument('--no-cpu-baseline', action='store_true',
+                    help='with --full: skip the CPU baselines')
     ap.add_argument('--n-samples', type=int, default=N,
                     help='headline N (profiling passes only; the metric is quoted at 128)')
     ap.add_argument('--legs', default='all',
-                    help="'all', 'none' or a comma list of cfg3_256,cfg1,cfg2,cfg4,cfg5,khat")
+                    help="with --full: 'all', 'none' or a comma list of "
+                         "cfg3_256,cfg1,cfg2,cfg4,cfg5,khat")
     args = ap.parse_args()
+    if not args.full and args.legs not in ('all', 'none'):
+        ap.error('--legs %s needs --full' % args.legs)
 
     import numpy as np
     import torch
@@ -821,7 +864,10 @@ def main():
     roof, valu = roofline_cfg3(launches, NS, traffic)
 
     # restart summaries gathered over RCCL (the only collective)
-    lam, hist, vals, smooth = run.result()
+    # (the history rows are copied back only when they are to be written out)
+    lam, hist, vals, smooth = run.result(history=bool(args.dump_outputs))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, lam, hist, vals, smooth)
     summary = torch.tensor([float(vals[0, -1]), float(np.mean(vals[0, -100:])),
                             float(np.linalg.norm(smooth[0]))], dtype=torch.float64,
                            device=coll_device(dev))
@@ -833,12 +879,12 @@ def main():
         gathered = summary.cpu().numpy()[None]
     value = world * K * NS * D / elapsed
 
-    legs = [] if args.legs == 'none' else (
+    legs = [] if args.legs == 'none' or not args.full else (
         ['cfg3_256', 'cfg1', 'cfg2', 'cfg4', 'cfg5', 'khat'] if args.legs == 'all'
         else args.legs.split(','))
     if world > 1:
         legs = [l for l in legs if l == 'cfg5']      # the sharded config; others are per-GPU
-    cpu = not args.no_cpu_baseline and world == 1 and rank == 0
+    cpu = args.full and not args.no_cpu_baseline and world == 1 and rank == 0
     host = host_info() if cpu else None
     configs = {}
     for leg in legs:
@@ -863,7 +909,7 @@ def main():
             print('[bench] leg %s done in %.1f s' % (leg, configs[leg]['leg_seconds']),
                   file=sys.stderr, flush=True)
 
-    measured = measure_peaks() if rank == 0 else None
+    measured = measure_peaks() if args.full and rank == 0 else None
     add_measured(roof, measured, 'hbm_copy')
     if valu and measured and measured.get('valu_fma_f64'):
         valu['measured_fma_f64_peak'] = measured['valu_fma_f64']
@@ -881,7 +927,7 @@ def main():
             'metric': METRIC,
             'value': value, 'unit': 'MC-samples/s', 'n_gpus': world, 'steps': K, 'warmup': W,
             'ms_per_step': elapsed / K * 1e3, 'higher_is_better': True, 'scaling': 'weak',
-            'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
+            'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic', 'full': args.full,
             'config': {'workload': 'mean-field Gaussian KLVI + adagrad on isotropic Gaussian '
                                    'target (SURVEY config 3)',
                        'D': D, 'N': NS, 'window': WINDOW, 'learning_rate': LR, 'epsilon': EPS,

@@ -11,7 +11,7 @@ timeout -k 10 400 python -u -m pytest ${TESTS:-tests/test_gpu_vb.py tests/test_g
 rc=$?; tail -3 gpurun_out/pytest_pf.log; [ $rc -ne 0 ] && exit $rc
 for i in $(seq 1 ${ROUNDS:-3}); do
   for pf in 0 1; do
-    VIABEL_AMD_BLOCK_PF=$pf timeout -k 10 200 python bench.py --legs ${LEGS:-cfg1,cfg2,cfg5} --no-cpu-baseline \
+    VIABEL_AMD_BLOCK_PF=$pf timeout -k 10 200 python bench.py --full --legs ${LEGS:-cfg1,cfg2,cfg5} --no-cpu-baseline \
       --steps 20 --warmup 5 > gpurun_out/ab_pf_$pf.json 2> gpurun_out/ab_pf_$pf.err || exit $?
     python - "$pf" <<'PY'
 import json, sys

@@ -22,7 +22,7 @@ for i in $(seq 1 ${ROUNDS:-3}); do
     # "name+VAR=value": the library plus an environment switch
     name=${L%%+*}; envv=""; [ "$name" != "$L" ] && envv=${L#*+}
     lib=$PWD/viabel_amd/libviabel_amd_$name.so; [ "$name" = new ] && lib=$PWD/viabel_amd/libviabel_amd.so
-    env $envv VIABEL_AMD_LIB=$lib timeout -k 10 200 python bench.py --legs ${LEGS:-cfg1,cfg2,cfg5} --no-cpu-baseline \
+    env $envv VIABEL_AMD_LIB=$lib timeout -k 10 200 python bench.py --full --legs ${LEGS:-cfg1,cfg2,cfg5} --no-cpu-baseline \
       --steps 20 --warmup 5 > gpurun_out/ab_legs.json 2> gpurun_out/ab_legs.err || exit $?
     python - "$L" <<'PY'
 import json, sys

@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 for i in $(seq 1 ${ROUNDS:-3}); do
   for pd in t all; do
-    VIABEL_AMD_PREDRAW=$pd timeout -k 10 200 python bench.py --legs cfg1 --no-cpu-baseline \
+    VIABEL_AMD_PREDRAW=$pd timeout -k 10 200 python bench.py --full --legs cfg1 --no-cpu-baseline \
       --steps 20 --warmup 5 > gpurun_out/ab_pd.json 2> gpurun_out/ab_pd.err || exit $?
     python - "$pd" <<'PY'
 import json, sys

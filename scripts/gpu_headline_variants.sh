@@ -10,6 +10,6 @@ run() {
 }
 for i in 1 2 3; do
   run --legs none --no-cpu-baseline
-  run --legs none
-  run --legs cfg1 --no-cpu-baseline
+  run --full --legs none
+  run --full --legs cfg1 --no-cpu-baseline
 done

@@ -14,7 +14,9 @@ if [ -f viabel_amd/libviabel_amd_base.so ]; then
 fi
 timeout -k 10 600 python -u -m pytest tests -m gpu -q --timeout 300 --timeout-method thread > gpurun_out/pytest_gpu.log 2>&1
 tail -3 gpurun_out/pytest_gpu.log
-timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/bench.log 2>&1
-tail -c 600 gpurun_out/bench.log
+REC=${REC:-bench_out}
+mkdir -p $REC
+timeout -k 10 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $REC/bench.log 2>&1
+tail -c 600 $REC/bench.log
 PASSES=trace bash scripts/profile_r02.sh > /dev/null
 bash scripts/gpu_fr_prof.sh

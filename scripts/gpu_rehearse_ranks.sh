@@ -9,7 +9,7 @@ mkdir -p gpurun_out
 # (bench.py picks gloo itself when local ranks outnumber the GPUs)
 for n in ${RANKS:-2 4}; do
   timeout -k 10 240 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n \
-    --master-addr 127.0.0.1 --master-port $((29500 + n)) bench.py --gpus $n --steps 20 --warmup 5 \
+    --master-addr 127.0.0.1 --master-port $((29500 + n)) bench.py --full --gpus $n --steps 20 --warmup 5 \
     > gpurun_out/rehearse_$n.log 2> gpurun_out/rehearse_$n.err || { tail -20 gpurun_out/rehearse_$n.err; exit 1; }
   python - "$n" <<'PY'
 import json, sys

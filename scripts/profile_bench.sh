@@ -5,7 +5,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
-ARGS=${ARGS:-"--steps 5120 --warmup 512 --no-cpu-baseline"}
+ARGS=${ARGS:-"--full --steps 5120 --warmup 512 --no-cpu-baseline"}
 OUT=gpurun_out/prof
 mkdir -p $OUT
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- python3 bench.py $ARGS > $OUT/trace.log 2>&1 || exit $?
