@@ -84,10 +84,30 @@ enum vb_target_kind {
   VB_TARGET_EIGHT_SCHOOLS_NCP = 3, /* eight_schools_ncp.stan log_prob, D = 10              */
   VB_TARGET_CORR_GAUSS = 4,   /* N(0, Sigma*): params = [inv(Sigma*) (D x D row-major),
                                  log normaliser]; full-rank family only (SURVEY §8d cfg 4) */
-  VB_TARGET_CALLBACK = 5      /* user model through vb_target.callback (make_stan_log_density,
+  VB_TARGET_CALLBACK = 5,     /* user model through vb_target.callback (make_stan_log_density,
                                  vb.py:314-321): evaluated on the host once per step on the
                                  batch of samples; everything else stays on the device */
+  VB_TARGET_REGRESSION = 6    /* generalised linear model over a data matrix in `params`
+                                 (layout below), evaluated on the device; any family, any D */
 };
+
+/* VB_TARGET_REGRESSION: log p(beta) = sum_d log N(beta_d; 0, s^2) + sum_m l(y_m, eta_m),
+ * eta_m = x_m . beta, every normalising constant kept:
+ *   gaussian         l = log N(y; eta, sigma^2)
+ *   student_t        l = log t_nu(y; eta, sigma)
+ *   bernoulli_logit  l = y eta - softplus(eta)
+ * vb_target.params (host or device memory; dim = D):
+ *   params[0] likelihood: 0 gaussian, 1 student_t, 2 bernoulli_logit
+ *   params[1] M (number of observations, >= 1, integral)
+ *   params[2] nu   (student_t degrees of freedom, > 0; ignored otherwise)
+ *   params[3] sigma (gaussian / student_t scale, > 0; ignored for bernoulli_logit)
+ *   params[4] prior_scale s (> 0): beta_d ~ N(0, s^2) independently
+ *   params[5..7] reserved, zero
+ *   params[8 ..]          X, row-major [M][D]
+ *   params[8 + M*D ..]    y [M]   (bernoulli_logit: 0 or 1)
+ *   n_params = 8 + M*D + M
+ * vb_run_create copies the block once into the run; one-shot calls stage a host
+ * block per call and read a device block in place. */
 
 /* User target: log p and d log p / dx of the n rows of x [n][d] (HOST memory,
  * C order) into logp [n] and grad [n][d]; return 0, or non-zero to abort the

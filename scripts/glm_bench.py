@@ -1,0 +1,95 @@
+"""Step time of adagrad_optimize for one regression model evaluated two ways:
+through targets.callback (the numpy restatement, on the host once per step) and
+through targets.regression (on the device).  Prints one JSON line per case.
+
+  case i   D = 2,  M = 25,      N = 100, mean-field t (robust-regression.ipynb)
+  case ii  D = 32, M = 100 000, N = 128, mean-field Gaussian
+
+Each timing is a whole adagrad_optimize call of --steps iterations divided by the
+step count; the device is synchronised before both clocks; --warmup untimed calls,
+then the median of --reps.  --device-only skips the callback path (for a kernel
+trace of the device path alone).
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from tests import glm_cases as gc  # noqa: E402
+from tests import notebook_cases as nc  # noqa: E402
+
+CASES = {
+    'i': dict(D=2, M=25, N=100, family='mf_t', df=40.0, steps=200),
+    'ii': dict(D=32, M=100000, N=128, family='mf_gauss', df=5.0, steps=20),
+}
+
+
+def _time(fn, sync, warmup, reps):
+    for _ in range(warmup):
+        fn()
+    out = []
+    for _ in range(reps):
+        sync()
+        t0 = time.perf_counter()
+        fn()
+        sync()
+        out.append(time.perf_counter() - t0)
+    return out
+
+
+def run_case(name, steps, warmup, reps, device_only):
+    from viabel_amd import vb, targets, _native as nat
+    c = CASES[name]
+    D, N = c['D'], c['N']
+    steps = steps or c['steps']
+    if name == 'i':
+        x, y = nc.robust_regression_data()
+        kw = dict(likelihood='student_t', df=40.0, scale=1.0, prior_scale=10.0)
+    else:
+        x, y = gc.make_data(D, c['M'], 'student_t', seed=1, df=c['df'], scale=0.7)
+        kw = dict(likelihood='student_t', df=c['df'], scale=0.7, prior_scale=3.0)
+
+    def family():
+        if c['family'] == 'mf_t':
+            return vb.mean_field_t_variational_family(D, c['df'], rng='numpy')
+        return vb.mean_field_gaussian_variational_family(D, rng='numpy')
+
+    init = np.zeros(2 * D)
+    sync = nat.context().synchronize
+    paths = {'device': targets.regression(x, y, **kw)}
+    if not device_only:
+        paths['callback'] = targets.callback(gc.restatement(x, y, **kw), D)
+    res = dict(case=name, D=D, M=int(x.shape[0]), N=N, family=c['family'], steps=steps,
+               warmup=warmup, reps=reps)
+    for label, tgt in paths.items():
+        obj = vb.black_box_klvi(family(), tgt, N)
+        ts = _time(lambda: vb.adagrad_optimize(steps, obj, init), sync, warmup, reps)
+        res[label + '_us_per_step'] = 1e6 * statistics.median(ts) / steps
+        res[label + '_us_per_step_all'] = [round(1e6 * t / steps, 2) for t in ts]
+    if not device_only:
+        res['callback_over_device'] = res['callback_us_per_step'] / res['device_us_per_step']
+    print(json.dumps(res), flush=True)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--case', default='all', choices=['all', 'i', 'ii'])
+    ap.add_argument('--steps', type=int, default=0, help='iterations per call (0: the case default)')
+    ap.add_argument('--warmup', type=int, default=2)
+    ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--device-only', action='store_true')
+    a = ap.parse_args()
+    for name in (['i', 'ii'] if a.case == 'all' else [a.case]):
+        run_case(name, a.steps, a.warmup, a.reps, a.device_only)
+
+
+if __name__ == '__main__':
+    main()

@@ -554,9 +554,48 @@ int check_family(const vb_family* f, FamInfo* o) {
   return VB_OK;
 }
 
-int check_target(const vb_target* t, int D) {
+// Header of a regression target's parameter block (include/viabel_amd.h), read from
+// host or device memory and checked against n_params and dim.
+int regression_head(const vb_target* t, vbk::GlmHead* o) {
+  if (!t->params || t->n_params < vbk::kGlmHeader)
+    return fail(VB_EINVAL, "regression target: n_params %lld is shorter than the %d-value header",
+                (long long)t->n_params, vbk::kGlmHeader);
+  double h[vbk::kGlmHeader];
+  const int pc = ptr_class(t->params);
+  if (pc < 0) return foreign_ptr_error(t->params);
+  if (pc == 1)
+    VB_HIP(hipMemcpy(h, t->params, sizeof h, hipMemcpyDeviceToHost));
+  else
+    std::memcpy(h, t->params, sizeof h);
+  if (!(h[0] == 0.0 || h[0] == 1.0 || h[0] == 2.0))
+    return fail(VB_EINVAL, "regression target: params[0] (likelihood) must be 0, 1 or 2, got %g", h[0]);
+  if (!(h[1] >= 1.0 && h[1] <= 9.0e15 && h[1] == std::floor(h[1])))
+    return fail(VB_EINVAL, "regression target: params[1] (M) must be an integer >= 1, got %g", h[1]);
+  const int lik = (int)h[0];
+  if (lik == 1 && !(h[2] > 0.0 && std::isfinite(h[2])))
+    return fail(VB_EINVAL, "regression target: params[2] (nu) must be positive, got %g", h[2]);
+  if (lik != 2 && !(h[3] > 0.0 && std::isfinite(h[3])))
+    return fail(VB_EINVAL, "regression target: params[3] (sigma) must be positive, got %g", h[3]);
+  if (!(h[4] > 0.0 && std::isfinite(h[4])))
+    return fail(VB_EINVAL, "regression target: params[4] (prior_scale) must be positive, got %g", h[4]);
+  for (int i = 5; i < vbk::kGlmHeader; ++i)
+    if (h[i] != 0.0)
+      return fail(VB_EINVAL, "regression target: params[%d] (reserved) must be zero, got %g", i, h[i]);
+  const double want = (double)vbk::kGlmHeader + h[1] * (double)t->dim + h[1];
+  if ((double)t->n_params != want)
+    return fail(VB_EINVAL, "regression target: n_params %lld does not match 8 + M*D + M = %.0f (M %.0f, dim %lld)",
+                (long long)t->n_params, want, h[1], (long long)t->dim);
+  o->lik = lik;
+  o->M = (long long)h[1];
+  o->nu = h[2];
+  o->sigma = h[3];
+  o->prior = h[4];
+  return VB_OK;
+}
+
+int check_target(const vb_target* t, int D, vbk::GlmHead* glm = nullptr) {
   if (!t) return fail(VB_EINVAL, "null vb_target");
-  if (t->kind < VB_TARGET_ISOGAUSS || t->kind > VB_TARGET_CALLBACK)
+  if (t->kind < VB_TARGET_ISOGAUSS || t->kind > VB_TARGET_REGRESSION)
     return fail(VB_EUNSUPPORTED, "target kind %d is not implemented on the device", t->kind);
   if (t->kind == VB_TARGET_CALLBACK && !t->callback)
     return fail(VB_EINVAL, "callback target needs a callback");
@@ -569,7 +608,17 @@ int check_target(const vb_target* t, int D) {
   if (t->kind == VB_TARGET_FUNNEL && D < 2) return fail(VB_EINVAL, "funnel target needs D >= 2");
   if (t->kind == VB_TARGET_EIGHT_SCHOOLS_NCP && D != 10)
     return fail(VB_EINVAL, "eight_schools_ncp target has dimension 10, got %d", D);
+  if (t->kind == VB_TARGET_REGRESSION) {
+    vbk::GlmHead h{};
+    VB_TRY(regression_head(t, &h));
+    if (glm) *glm = h;
+  }
   return VB_OK;
+}
+
+// the kinds that always take the materialised path (no block / rows kernel)
+bool materialised_target(int kind) {
+  return kind == VB_TARGET_CALLBACK || kind == VB_TARGET_REGRESSION;
 }
 
 void key_of(uint64_t seed, uint32_t* k0, uint32_t* k1) {
@@ -581,6 +630,12 @@ void key_of(uint64_t seed, uint32_t* k0, uint32_t* k1) {
 int target_params(vb_ctx* c, int s, const vb_target* t, const double** dev, double* tconst) {
   *dev = nullptr;
   *tconst = 0.0;
+  if (t->kind == VB_TARGET_REGRESSION) {   // the whole block; a device pointer is used in place
+    In in;
+    VB_TRY(in.stage(c, s, t->params, (size_t)t->n_params));
+    *dev = in.d;
+    return VB_OK;
+  }
   if (t->kind != VB_TARGET_CORR_GAUSS) return VB_OK;
   const size_t dd = (size_t)t->dim * t->dim;
   In in;
@@ -614,8 +669,9 @@ vbk::HostTarget host_of(const vb_target* t) {
 }
 
 vbk::FrSpec fr_spec(const FamInfo& fi, const vb_target* tgt, const vb_objective* obj,
-                    const double* tparams, double tconst) {
+                    const double* tparams, double tconst, const vbk::GlmHead& glm) {
   vbk::FrSpec f{};
+  f.glm = glm;
   f.host = host_of(tgt);
   f.D = fi.D;
   f.N = (int)obj->n_samples;
@@ -639,8 +695,11 @@ double sep_c0(const FamInfo& fi, bool pd) {
   return pd ? 0.5 * D * std::log(2 * M_PI) : 0.5 * D * (1.0 + std::log(2 * M_PI));
 }
 
-vbk::MfSpec mf_spec(const FamInfo& fi, const vb_target* tgt, const vb_objective* obj) {
+vbk::MfSpec mf_spec(const FamInfo& fi, const vb_target* tgt, const vb_objective* obj,
+                    const double* tparams, const vbk::GlmHead& glm) {
   vbk::MfSpec f{};
+  f.tparams = tparams;
+  f.glm = glm;
   f.host = host_of(tgt);
   f.fam = fi.kind;
   f.D = fi.D;
@@ -658,7 +717,8 @@ vbk::MfSpec mf_spec(const FamInfo& fi, const vb_target* tgt, const vb_objective*
 
 // vb_objective_value_grad for the full-rank t family
 int fr_objective(vb_ctx* c, const FamInfo& fi, const vb_target* tgt, const vb_objective* obj,
-                 const double* lam, const vb_noise* noise, double* value, double* grad) {
+                 const double* lam, const vb_noise* noise, double* value, double* grad,
+                 const vbk::GlmHead& glm) {
   const bool host = noise->kind == VB_NOISE_HOST;
   if (host && !noise->eps) return fail(VB_EINVAL, "host noise requires eps");
   const size_t N = (size_t)obj->n_samples;
@@ -669,7 +729,7 @@ int fr_objective(vb_ctx* c, const FamInfo& fi, const vb_target* tgt, const vb_ob
   VB_TRY(dg.stage(c, 2, grad, fi.P));
   const double* tp;
   double tc;
-  VB_TRY(target_params(c, 3, tgt, &tp, &tc));
+  VB_TRY(target_params(c, tgt->kind == VB_TARGET_REGRESSION ? 8 : 3, tgt, &tp, &tc));
   VB_TRY(c->slot[4].reserve(sizeof(double) * 2));
   uint32_t k0, k1;
   key_of(noise->seed, &k0, &k1);
@@ -678,7 +738,7 @@ int fr_objective(vb_ctx* c, const FamInfo& fi, const vb_target* tgt, const vb_ob
   // a root or gradient solve that needed more iterations than launched (an
   // ill-conditioned Sigma) runs the call again with larger counts (fr_info)
   for (int attempt = 0;; ++attempt) {
-    VB_TRY(vbk::fr_value_grad(W, fr_spec(fi, tgt, obj, tp, tc), dl.d, host ? dn.d : nullptr, k0,
+    VB_TRY(vbk::fr_value_grad(W, fr_spec(fi, tgt, obj, tp, tc, glm), dl.d, host ? dn.d : nullptr, k0,
                               k1, noise->stream, (uint32_t)noise->step, c->slot[4].d(), dg.d,
                               c->stream));
     VB_TRY(sync(c));
@@ -876,7 +936,8 @@ int vb_target_logdensity(vb_ctx* c, const vb_target* tgt, const double* x, int64
                          double* out, double* grad_out) {
   VB_TRY(check_ctx(c));
   if (!tgt) return fail(VB_EINVAL, "null target");
-  VB_TRY(check_target(tgt, (int)tgt->dim));
+  vbk::GlmHead glm{};
+  VB_TRY(check_target(tgt, (int)tgt->dim, &glm));
   if (!x || !out || n < 0) return fail(VB_EINVAL, "null argument");
   const int D = (int)tgt->dim;
   In dxx;
@@ -889,6 +950,14 @@ int vb_target_logdensity(vb_ctx* c, const vb_target* tgt, const double* x, int64
     vbk::FrWork* W;
     VB_TRY(fr_work(c, &W));
     VB_TRY(vbk::host_target_eval(W, host_of(tgt), D, n, dxx.d, dout.d, dg.d, c->stream));
+  } else if (tgt->kind == VB_TARGET_REGRESSION) {
+    if (n == 0) return VB_OK;
+    const double* tp;
+    double tc;
+    VB_TRY(target_params(c, 8, tgt, &tp, &tc));
+    vbk::FrWork* W;
+    VB_TRY(fr_work(c, &W));
+    VB_TRY(vbk::glm_target_eval(W, glm, D, n, tp, dxx.d, dout.d, dg.d, c->stream));
   } else if (tgt->kind == VB_TARGET_CORR_GAUSS) {
     if (n == 0) return VB_OK;
     const double* tp;
@@ -912,7 +981,8 @@ int vb_objective_value_grad(vb_ctx* c, const vb_family* fam, const vb_target* tg
   VB_TRY(check_ctx(c));
   FamInfo fi;
   VB_TRY(check_family(fam, &fi));
-  VB_TRY(check_target(tgt, fi.D));
+  vbk::GlmHead glm{};
+  VB_TRY(check_target(tgt, fi.D, &glm));
   if (!obj || !lam || !noise || !value || !grad) return fail(VB_EINVAL, "null argument");
   if (obj->n_samples < 1 || obj->n_samples > (1LL << 31))
     return fail(VB_EINVAL, "n_samples must be positive");
@@ -921,7 +991,7 @@ int vb_objective_value_grad(vb_ctx* c, const vb_family* fam, const vb_target* tg
   if (obj->kind == VB_OBJ_CHIVI && !(obj->alpha > 0))
     return fail(VB_EINVAL, "alpha must be positive");
   VB_TRY(require_fr(fi.kind, tgt->kind));
-  if (fi.kind == VB_FAMILY_FR_T) return fr_objective(c, fi, tgt, obj, lam, noise, value, grad);
+  if (fi.kind == VB_FAMILY_FR_T) return fr_objective(c, fi, tgt, obj, lam, noise, value, grad, glm);
   const int D = fi.D, N = (int)obj->n_samples;
   const size_t P = 2 * (size_t)D;
   const bool host = noise->kind == VB_NOISE_HOST;
@@ -942,7 +1012,7 @@ int vb_objective_value_grad(vb_ctx* c, const vb_family* fam, const vb_target* tg
 
   const bool pd = obj->kind == VB_OBJ_KLVI_PD;
   const bool sep = vbk::target_separable(tgt->kind) && obj->kind != VB_OBJ_CHIVI;
-  const bool cb = tgt->kind == VB_TARGET_CALLBACK;
+  const bool cb = materialised_target(tgt->kind);
   if (sep && D > vbk::kBlockDMax) {
     vbk::SepArgs a{};
     a.D = D;
@@ -1013,9 +1083,12 @@ int vb_objective_value_grad(vb_ctx* c, const vb_family* fam, const vb_target* tg
     }
   } else {
     // CHIVI or a non-separable target at D > kBlockDMax: materialised path
+    const double* tp;
+    double tc;
+    VB_TRY(target_params(c, 8, tgt, &tp, &tc));
     vbk::FrWork* W;
     VB_TRY(fr_work(c, &W));
-    VB_TRY(vbk::mf_wide_value_grad(W, mf_spec(fi, tgt, obj), c->slot[3].d(), host ? dn.d : nullptr,
+    VB_TRY(vbk::mf_wide_value_grad(W, mf_spec(fi, tgt, obj, tp, glm), c->slot[3].d(), host ? dn.d : nullptr,
                                    k0, k1, noise->stream, (uint32_t)noise->step, dval, dg.d,
                                    c->stream));
   }
@@ -1090,7 +1163,8 @@ int vb_run_create(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const v
   *out = nullptr;
   FamInfo fi;
   VB_TRY(check_family(fam, &fi));
-  VB_TRY(check_target(tgt, fi.D));
+  vbk::GlmHead glm{};
+  VB_TRY(check_target(tgt, fi.D, &glm));
   VB_TRY(require_fr(fi.kind, tgt->kind));
   if (!obj || !cfg || !init) return fail(VB_EINVAL, "null argument");
   if (!(cfg->learning_rate > 0)) return fail(VB_EINVAL, "learning rate must be positive");
@@ -1116,7 +1190,7 @@ int vb_run_create(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const v
   // materialised path, whose window lives in HBM)
   const bool big_window = !ia && cfg->window > 64;
   const bool wide = !fr && ((D > vbk::kBlockDMax && (!sep || ia)) ||
-                            tgt->kind == VB_TARGET_CALLBACK || big_window);
+                            materialised_target(tgt->kind) || big_window);
   if (sep && n_problems != 1)
     return fail(VB_EUNSUPPORTED, "wide (D > %d) runs hold one problem per vb_run", vbk::kBlockDMax);
 
@@ -1150,23 +1224,30 @@ int vb_run_create(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const v
     return rc;
   };
   int rc;
-  if (wide) {
-    if ((rc = r->grad.reserve(sizeof(double) * P)) != VB_OK) return bail(rc);
-    r->mspec = mf_spec(fi, tgt, obj);
-  }
-  if (fr) {
-    r->fr = true;
+  // the target's parameter block is copied once into the run; its steps read it from
+  // there (the caller's pointer is not kept)
+  const double* run_tp = nullptr;
+  double tc = 0.0;
+  if (fr || (wide && tgt->kind == VB_TARGET_REGRESSION)) {
     const double* tp;
-    double tc;
     if ((rc = target_params(c, 1, tgt, &tp, &tc)) != VB_OK) return bail(rc);
+    run_tp = tp;
     if (tp) {
       const size_t np = (size_t)tgt->n_params;
       if ((rc = r->tparams.reserve(sizeof(double) * np)) != VB_OK) return bail(rc);
       hipError_t e = hipMemcpyAsync(r->tparams.p, tp, sizeof(double) * np, hipMemcpyDeviceToDevice,
                                     c->stream);
       if (e != hipSuccess) return bail(fail(VB_EDEVICE, "hipMemcpy failed: %s", hipGetErrorString(e)));
+      run_tp = r->tparams.d();
     }
-    r->spec = fr_spec(fi, tgt, obj, r->tparams.d(), tc);
+  }
+  if (wide) {
+    if ((rc = r->grad.reserve(sizeof(double) * P)) != VB_OK) return bail(rc);
+    r->mspec = mf_spec(fi, tgt, obj, run_tp, glm);
+  }
+  if (fr) {
+    r->fr = true;
+    r->spec = fr_spec(fi, tgt, obj, run_tp, tc, glm);
     if ((rc = r->grad.reserve(sizeof(double) * P)) != VB_OK) return bail(rc);
   }
   if ((rc = r->lam.reserve(sizeof(double) * P * n_problems)) != VB_OK) return bail(rc);
@@ -1710,7 +1791,7 @@ int vb_log_weights_rows(vb_ctx* c, const vb_family* fam, const vb_target* tgt,
   if (rows > 65535) return fail(VB_EINVAL, "rows must be <= 65535");
   if (fi.kind == VB_FAMILY_FR_T) return fail(VB_EUNSUPPORTED, "rows of log weights: mean-field families only");
   if (noise->kind != VB_NOISE_PHILOX) return fail(VB_EINVAL, "rows of log weights need Philox noise");
-  if ((!vbk::target_separable(tgt->kind) && fi.D > vbk::kBlockDMax) || tgt->kind == VB_TARGET_CALLBACK)
+  if ((!vbk::target_separable(tgt->kind) && fi.D > vbk::kBlockDMax) || materialised_target(tgt->kind))
     return fail(VB_EUNSUPPORTED, "rows of log weights: D <= %d or a separable device target",
                 vbk::kBlockDMax);
   if (m == 0 || rows == 0) return VB_OK;
@@ -1733,7 +1814,8 @@ int vb_log_weights(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const 
   VB_TRY(check_ctx(c));
   FamInfo fi;
   VB_TRY(check_family(fam, &fi));
-  VB_TRY(check_target(tgt, fi.D));
+  vbk::GlmHead glm{};
+  VB_TRY(check_target(tgt, fi.D, &glm));
   if (!lam || !noise || !lw_out || m < 0) return fail(VB_EINVAL, "null argument");
   VB_TRY(require_fr(fi.kind, tgt->kind));
   if (fi.kind == VB_FAMILY_FR_T) {
@@ -1748,8 +1830,9 @@ int vb_log_weights(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const 
     VB_TRY(dxs.stage(c, 3, samples_out, samples_out ? (size_t)m * fi.D : 0));
     const double* tp;
     double tc;
-    VB_TRY(target_params(c, 4, tgt, &tp, &tc));
+    VB_TRY(target_params(c, tgt->kind == VB_TARGET_REGRESSION ? 8 : 4, tgt, &tp, &tc));
     vbk::FrSpec f{};
+    f.glm = glm;
     f.host = host_of(tgt);
     f.D = fi.D;
     f.tgt = tgt->kind;
@@ -1768,7 +1851,7 @@ int vb_log_weights(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const 
     return sync(c);
   }
   if ((!vbk::target_separable(tgt->kind) && fi.D > vbk::kBlockDMax) ||
-      tgt->kind == VB_TARGET_CALLBACK) {
+      materialised_target(tgt->kind)) {
     const bool host = noise->kind == VB_NOISE_HOST;
     if (host && !noise->eps) return fail(VB_EINVAL, "host noise requires eps");
     if (m == 0) return VB_OK;
@@ -1782,7 +1865,10 @@ int vb_log_weights(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const 
     key_of(noise->seed, &k0, &k1);
     vbk::FrWork* W;
     VB_TRY(fr_work(c, &W));
-    VB_TRY(vbk::mf_wide_log_weights(W, mf_spec(fi, tgt, nullptr), dl.d, m, host ? dn.d : nullptr,
+    const double* tp;
+    double tc;
+    VB_TRY(target_params(c, 8, tgt, &tp, &tc));
+    VB_TRY(vbk::mf_wide_log_weights(W, mf_spec(fi, tgt, nullptr, tp, glm), dl.d, m, host ? dn.d : nullptr,
                                     k0, k1, noise->stream, (uint32_t)noise->step, dlw.d, dxs.d,
                                     c->stream));
     VB_TRY(dlw.finish(c));

@@ -1450,6 +1450,7 @@ struct FrWork {
   } wsnap_h{};
   // N x D / N
   Buf Z, X, G, s, logp, zz, r, rk;
+  Buf glm;  // regression target: chunk partials (glm_target_eval)
   // pinned host staging for host-callback targets
   double *hx = nullptr, *hlp = nullptr, *hg = nullptr;
   size_t hcap = 0;
@@ -1570,10 +1571,20 @@ int host_target_eval(FrWork* W, const HostTarget& t, int D, long long n, const d
   return 0;
 }
 
+int glm_target_eval(FrWork* W, const GlmHead& h, int D, long long n, const double* tparams,
+                    const double* x, double* logp, double* grad, hipStream_t st) {
+  if (!tparams) return vb_set_error(-1, "regression target without parameters");
+  FR_HIP(W->glm.reserve(sizeof(double) * glm_scratch_doubles(D, n, h.M, grad != nullptr)));
+  FR_HIP(launch_glm_rows(D, n, h, tparams, x, logp, grad, W->glm.d(), st));
+  return 0;
+}
+
 namespace {
-int eval_target(FrWork* W, int tgt, const HostTarget& host, int D, long long n, const double* x,
-                double* logp, double* grad, hipStream_t st) {
+int eval_target(FrWork* W, int tgt, const HostTarget& host, const double* tparams,
+                const GlmHead& glm, int D, long long n, const double* x, double* logp,
+                double* grad, hipStream_t st) {
   if (tgt == kTargetCallback) return host_target_eval(W, host, D, n, x, logp, grad, st);
+  if (tgt == kTargetRegression) return glm_target_eval(W, glm, D, n, tparams, x, logp, grad, st);
   FR_HIP(launch_target_logdensity(tgt, D, n, x, logp, grad, st));
   return 0;
 }
@@ -1989,7 +2000,7 @@ int fr_value_grad(FrWork* W, const FrSpec& f, const double* lam, const double* h
                          (f.chivi || f.pd) ? z : nullptr, W->X.d(), W->G.d(), f.tconst, 1,
                          W->zz.d(), W->logp.d());
   } else {
-    if (int rc = eval_target(W, f.tgt, f.host, D, N, W->X.d(), W->logp.d(), W->G.d(), st)) return rc;
+    if (int rc = eval_target(W, f.tgt, f.host, f.tparams, f.glm, D, N, W->X.d(), W->logp.d(), W->G.d(), st)) return rc;
     if (!fused && (f.chivi || f.pd))
       hipLaunchKernelGGL(fr_rows_kernel, dim3(blocks(N, 4)), dim3(256), 0, st, D, (long long)N,
                          z, nullptr, nullptr, 0.0, 0, W->zz.d(), nullptr);
@@ -2107,7 +2118,7 @@ int fr_log_weights(FrWork* W, const FrSpec& f, const double* lam, long long m,
     hipLaunchKernelGGL(fr_rows_kernel, dim3(blocks(m, 4)), dim3(256), 0, st, D, m, z, x, W->G.d(),
                        f.tconst, 1, W->zz.d(), W->logp.d());
   } else {
-    if (int rc = eval_target(W, f.tgt, f.host, D, m, x, W->logp.d(), nullptr, st)) return rc;
+    if (int rc = eval_target(W, f.tgt, f.host, f.tparams, f.glm, D, m, x, W->logp.d(), nullptr, st)) return rc;
     hipLaunchKernelGGL(fr_rows_kernel, dim3(blocks(m, 4)), dim3(256), 0, st, D, m, z, nullptr,
                        nullptr, 0.0, 0, W->zz.d(), nullptr);
   }
@@ -2379,7 +2390,7 @@ int mf_wide_value_grad(FrWork* W, const MfSpec& f, const double* lam, const doub
   } else {
     FR_HIP(launch_sample(f.fam, D, N, lam, f.t_scale, f.shape, host_eps, k0, k1, stream, step,
                          W->X.d(), st));
-    if (int rc = eval_target(W, f.tgt, f.host, D, N, W->X.d(), W->logp.d(), W->G.d(), st))
+    if (int rc = eval_target(W, f.tgt, f.host, f.tparams, f.glm, D, N, W->X.d(), W->logp.d(), W->G.d(), st))
       return rc;
     if (f.chivi || f.pd)
       FR_HIP(launch_family_logdensity(f.fam, D, N, lam, f.df, f.t_const, W->X.d(), W->zz.d(), st));
@@ -2448,7 +2459,7 @@ int mf_wide_log_weights(FrWork* W, const MfSpec& f, const double* lam, long long
     FR_HIP(launch_sample(f.fam, D, m, lam, f.t_scale, f.shape, host_eps, k0, k1, stream, step, x,
                          st));
   }
-  if (int rc = eval_target(W, f.tgt, f.host, D, m, x, W->logp.d(), nullptr, st)) return rc;
+  if (int rc = eval_target(W, f.tgt, f.host, f.tparams, f.glm, D, m, x, W->logp.d(), nullptr, st)) return rc;
   FR_HIP(launch_family_logdensity(f.fam, D, m, lam, f.df, f.t_const, x, W->zz.d(), st));
   hipLaunchKernelGGL(sub_kernel, dim3(blocks(m)), dim3(256), 0, st, m, W->logp.d(), W->zz.d(), lw);
   FR_HIP(hipGetLastError());

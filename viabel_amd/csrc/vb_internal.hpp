@@ -192,6 +192,23 @@ int vb_set_error(int code, const char* fmt, ...);  // defined in vb_capi.hip
 constexpr int kFamilyFrT = 2;
 constexpr int kTargetCorrGauss = 4;
 constexpr int kTargetCallback = 5;
+constexpr int kTargetRegression = 6;
+// Regression target (vb_glm.hip): host copy of the parameter block's header
+// (include/viabel_amd.h); X [M][D] starts kGlmHeader doubles into the block.
+constexpr int kGlmHeader = 8;
+struct GlmHead {
+  int lik;            // 0 gaussian, 1 student_t, 2 bernoulli_logit
+  long long M;        // observations
+  double nu, sigma, prior;
+};
+// log p [n] and (grad non-null) d log p / dx [n][D] of the rows of x [n][D] for the
+// regression target whose parameter block is at `params` (device).  scratch holds
+// glm_scratch_doubles(D, n, M, grad != null) doubles of chunk partials (none for
+// one chunk).  Two identical calls give identical bits.
+size_t glm_scratch_doubles(int D, long long n, long long M, bool grad);
+hipError_t launch_glm_rows(int D, long long n, const GlmHead& h, const double* params,
+                           const double* x, double* logp, double* grad, double* scratch,
+                           hipStream_t s);
 // host model callback (vb_target_callback) + its user pointer
 struct HostTarget {
   int (*fn)(void* user, const double* x, int64_t n, int64_t d, double* logp, double* grad);
@@ -211,9 +228,10 @@ void fr_work_destroy(FrWork* w);
 struct FrSpec {
   int D, N, tgt, chivi, pd;
   double df, t_const, alpha;
-  const double* tparams;  // device; corr_gauss: P*[D][D]
+  const double* tparams;  // device; corr_gauss: P*[D][D]; regression: the parameter block
   double tconst;          // corr_gauss log normaliser
   HostTarget host;        // tgt == kTargetCallback
+  GlmHead glm;            // tgt == kTargetRegression
 };
 
 // All return 0 or a VB_E* code (message via vb_set_error).
@@ -230,6 +248,9 @@ int fr_transform(FrWork* W, int D, long long n, const double* mu, const double* 
                  const double* z, double* x, hipStream_t st);
 int fr_target(FrWork* W, int tgt, int D, long long n, const double* tparams, double tconst,
               const double* x, double* logp, double* G, hipStream_t st);
+// regression target at device x [n][D] (grad nullable); chunk partials in the workspace
+int glm_target_eval(FrWork* W, const GlmHead& h, int D, long long n, const double* tparams,
+                    const double* x, double* logp, double* grad, hipStream_t st);
 struct MfUpdate;
 // The next step of a fused run: its draws (rng step `step`) and L are prepared by
 // this step's last kernel when `prep`.
@@ -257,6 +278,8 @@ struct MfSpec {
   int fam, D, N, tgt, chivi, pd;
   double alpha, t_scale, shape, df, t_const;
   HostTarget host;  // tgt == kTargetCallback
+  const double* tparams;  // device; regression: the parameter block
+  GlmHead glm;            // tgt == kTargetRegression
 };
 // Optional windowed-adagrad step fused into the gradient pass (lam updated in
 // place, the step's gradient pushed into ring [W][P], new parameters copied to

@@ -14,6 +14,12 @@ Targets:
   eight_schools_ncp()    eight_schools_ncp.stan log_prob (D = 10)   eight-schools.ipynb
   corr_gauss(D)          N(0, A A^T / D + I), A = RandomState(512).randn(D, D)
                          (full-rank family)
+  regression(x, y, ...)  generalised linear model over a data matrix held on the
+                         device: beta ~ N(0, s^2 I), y_m | beta through a gaussian,
+                         student_t or bernoulli_logit link of x_m . beta
+                         (robust-regression.ipynb; VB_TARGET_REGRESSION)
+  robust_regression(x, y, df)   regression with the student_t likelihood
+  logistic_regression(x, y)     regression with the bernoulli_logit likelihood
 
 User models (the reference's make_stan_log_density, vb.py:314-321, and autograd
 callables): callback(fn, D), from_stan(fit, D) and torch_target(f, D) evaluate
@@ -27,6 +33,7 @@ import numpy as np
 from . import _native as nat
 
 __all__ = ['Target', 'isogauss', 'mixture', 'funnel', 'eight_schools_ncp', 'corr_gauss',
+           'regression', 'robust_regression', 'logistic_regression',
            'callback', 'from_stan', 'torch_target', 'as_target']
 
 
@@ -110,6 +117,66 @@ def corr_gauss(dim, seed=512):
     t = Target(nat.TARGET_CORR_GAUSS, dim, 'corr_gauss', np.concatenate([prec.ravel(), [const]]))
     t.sigma = sigma
     return t
+
+
+_LIKELIHOODS = {'gaussian': 0, 'student_t': 1, 'bernoulli_logit': 2}
+REGRESSION_HEADER = 8   # doubles before X in a regression target's parameter block
+
+
+def regression(x, y, likelihood='student_t', df=None, scale=1.0, prior_scale=10.0):
+    """A generalised linear model evaluated on the device: beta_d ~ N(0,
+    prior_scale^2) independently and, with eta_m = x_m . beta,
+      gaussian         y_m ~ N(eta_m, scale^2)
+      student_t        y_m ~ t_df(eta_m, scale)
+      bernoulli_logit  y_m ~ Bernoulli(logistic(eta_m)), y_m in {0, 1}
+    with every normalising constant kept.  x is (M, D), y is (M,).  The data are
+    packed once into one parameter array (layout in include/viabel_amd.h) that
+    the library uploads per run, so no host call happens inside a fit."""
+    if likelihood not in _LIKELIHOODS:
+        raise ValueError('unknown likelihood %r (expected one of %s)'
+                         % (likelihood, ', '.join(sorted(_LIKELIHOODS))))
+    x = np.asarray(x, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    if x.ndim != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError('x must be a non-empty (M, D) matrix, got shape %s' % (x.shape,))
+    if y.shape != (x.shape[0],):
+        raise ValueError('y must have shape (%d,), got %s' % (x.shape[0], y.shape))
+    if not (np.all(np.isfinite(x)) and np.all(np.isfinite(y))):
+        raise ValueError('x and y must be finite')
+    if not (np.isfinite(prior_scale) and prior_scale > 0):
+        raise ValueError('prior_scale must be positive')
+    if likelihood == 'student_t':
+        if df is None or not (np.isfinite(df) and df > 0):
+            raise ValueError('the student_t likelihood needs df > 0')
+    if likelihood != 'bernoulli_logit':
+        if not (np.isfinite(scale) and scale > 0):
+            raise ValueError('scale must be positive')
+    elif not np.all((y == 0) | (y == 1)):
+        raise ValueError('the bernoulli_logit likelihood needs y in {0, 1}')
+    m, d = x.shape
+    params = np.zeros(REGRESSION_HEADER + m * d + m)
+    params[0] = _LIKELIHOODS[likelihood]
+    params[1] = m
+    params[2] = df if likelihood == 'student_t' else 0.0
+    params[3] = scale if likelihood != 'bernoulli_logit' else 0.0
+    params[4] = prior_scale
+    params[REGRESSION_HEADER:REGRESSION_HEADER + m * d] = x.ravel()
+    params[REGRESSION_HEADER + m * d:] = y
+    t = Target(nat.TARGET_REGRESSION, d, 'regression', params)
+    t.likelihood = likelihood
+    t.n_obs = m
+    return t
+
+
+def robust_regression(x, y, df, scale=1.0, prior_scale=10.0):
+    """The reference's robust-regression model: y ~ student_t(df, x beta, scale),
+    beta ~ normal(0, prior_scale)."""
+    return regression(x, y, 'student_t', df=df, scale=scale, prior_scale=prior_scale)
+
+
+def logistic_regression(x, y, prior_scale=10.0):
+    """y ~ bernoulli_logit(x beta), beta ~ normal(0, prior_scale)."""
+    return regression(x, y, 'bernoulli_logit', prior_scale=prior_scale)
 
 
 def callback(logdensity_and_grad, dim=None, name='callback'):
