@@ -256,6 +256,17 @@ int vb_run_fr_retries(vb_run* run, int64_t* out);
  * (TFLOP/s), 3 fp64 FMA and 4 u64 multiply VALU issue (G wave-instructions/s)
  * over n iterations; best of reps timed launches on the context's stream. */
 int vb_peak_probe(vb_ctx* ctx, int32_t kind, int64_t n, int32_t reps, double* out);
+/* Device-math probe (test support, no reference counterpart): out[i] = helper fn
+ * at x[i], i < n, evaluated on the device by the inline function the kernels call
+ * (fn 0-12: exp_fast, expm1_pos, log_unit, log1p_pos_fast, sqrt_pos, sincospi_unit,
+ * log_unit_tab, log1p_pos_tab, log_u01_tab, sincospi_tab, cospi_tab_u24, the
+ * refined reciprocal and reciprocal square root) or by the library form it is
+ * measured against (fn 16-23: exp, expm1, log, log1p, sqrt, sinpi / cospi, 1 / x,
+ * 1 / sqrt(x)).  The sin / cos pairs (5, 9, 21) write sin to out and cos to out2
+ * (nullable; NaN for the other helpers); cospi_tab_u24 takes its 24-bit integer
+ * as a double.  An argument outside a table form's index range gives NaN. */
+int vb_math_probe(vb_ctx* ctx, int32_t fn, const double* x, int64_t n, double* out,
+                  double* out2);
 /* Launch timing (measurement support, no reference counterpart): with enable
  * != 0 every later vb_run_advance brackets its device work with HIP events on
  * the context's stream, one pair per kernel chunk (column-pair path) or per

@@ -33,24 +33,28 @@ def mixture(x):
     x = np.atleast_2d(x)
     a = _norm_logpdf(x, -2.0, 1.0)
     b = _norm_logpdf(x, 2.0, 1.0)
-    lp = np.sum(np.logaddexp(a, b) - np.log(2), axis=1)
-    wb = 1.0 / (1.0 + np.exp(a - b))
+    with np.errstate(under='ignore'):    # exp(-|4x|) -> 0 far from the modes
+        lp = np.sum(np.logaddexp(a, b) - np.log(2), axis=1)
+        # posterior weight of the +2 component, 1 / (1 + exp(a - b)) with a - b = -4x
+        # exactly; written on exp(-|4x|) <= 1 so that x << 0 does not overflow
+        e = np.exp(-np.abs(4.0 * x))
+        wb = np.where(x < 0, e / (1.0 + e), 1.0 / (1.0 + e))
     return lp, -(x + 2.0) + 4.0 * wb
 
 
 def funnel(x, s0=1.35):
     x = np.atleast_2d(x)
     v = x[:, 1]
-    lp = _norm_logpdf(v, 0.0, s0)
-    g = np.empty_like(x)
     scale = np.exp(v)
     others = [d for d in range(x.shape[1]) if d != 1]
-    gv = -v / s0 ** 2
-    for d in others:
-        lp = lp + _norm_logpdf(x[:, d], 0.0, scale)
-        g[:, d] = -x[:, d] * np.exp(-2 * v)
-        gv = gv + (x[:, d] / scale) ** 2 - 1.0
-    g[:, 1] = gv
+    # C order, so that the sums over axis 1 are numpy's pairwise sums: a running sum
+    # over the columns (a loop over d, or a reduction across a transposed layout)
+    # loses ~70 ulp of the sum's terms by D = 512 (tests/test_oracle_targets_mp.py)
+    xo = np.ascontiguousarray(x[:, others])
+    lp = _norm_logpdf(v, 0.0, s0) + np.sum(_norm_logpdf(xo, 0.0, scale[:, None]), axis=1)
+    g = np.empty_like(x)
+    g[:, others] = -xo * np.exp(-2 * v)[:, None]
+    g[:, 1] = -v / s0 ** 2 + np.sum((xo / scale[:, None]) ** 2 - 1.0, axis=1)
     return lp, g
 
 

@@ -90,6 +90,8 @@ _SIGNATURES = {
     'vb_run_fr_retries': ([ctypes.c_void_p, c_int64_p], ctypes.c_int),
     'vb_peak_probe': ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
                        c_double_p], ctypes.c_int),
+    'vb_math_probe': ([ctypes.c_void_p, ctypes.c_int32, c_double_p, ctypes.c_int64, c_double_p,
+                       c_double_p], ctypes.c_int),
     'vb_run_set_timing': ([ctypes.c_void_p, ctypes.c_int], ctypes.c_int),
     'vb_run_launch_times': ([ctypes.c_void_p, ctypes.c_int64, c_int64_p,
                              P(ctypes.c_float), c_int64_p], ctypes.c_int),
@@ -347,6 +349,24 @@ def block_floor_us(D, N, chivi=False, host_layout=False, n_steps=2000, n_problem
 
 
 PROBE_KINDS = {'hbm_copy': 0, 'hbm_read': 1, 'mfma_f64': 2, 'valu_fma_f64': 3, 'valu_mad_u64': 4}
+
+
+MATH_FNS = {'exp_fast': 0, 'expm1_pos': 1, 'log_unit': 2, 'log1p_pos_fast': 3, 'sqrt_pos': 4,
+            'sincospi_unit': 5, 'log_unit_tab': 6, 'log1p_pos_tab': 7, 'log_u01_tab': 8,
+            'sincospi_tab': 9, 'cospi_tab_u24': 10, 'rcp_refined': 11, 'rsqrt_pos': 12,
+            'exp': 16, 'expm1': 17, 'log': 18, 'log1p': 19, 'sqrt': 20, 'sincospi': 21,
+            'rcp': 22, 'rsqrt': 23}
+
+
+def math_probe(fn, x):
+    """One device math helper at every element of x (vb_math_probe): the vbd:: inline
+    function the kernels call, or its library counterpart.  Returns (out, out2);
+    out2 is the cosine of the sin / cos pairs and NaN otherwise.  Test support."""
+    x = as_f64(np.ravel(x))
+    out, out2 = np.empty_like(x), np.empty_like(x)
+    check(lib().vb_math_probe(context().handle, MATH_FNS[fn], dptr(x), x.size, dptr(out),
+                              dptr(out2)))
+    return out, out2
 
 
 def peak_probe(kind, n, reps=5):

@@ -205,9 +205,7 @@ struct Welf {
 
 __device__ __forceinline__ void welf_add(Welf& a, double v) {
   a.n += 1.0;
-  double inv = __builtin_amdgcn_rcp(a.n);          // 1 / count, refined (~1 ulp)
-  inv = fma(inv, fma(-a.n, inv, 1.0), inv);
-  inv = fma(inv, fma(-a.n, inv, 1.0), inv);
+  const double inv = rcp_refined(a.n);             // 1 / count
   const double d = v - a.mean;
   a.mean = fma(d, inv, a.mean);
   a.m2 = fma(d, v - a.mean, a.m2);

@@ -1639,6 +1639,21 @@ int vb_peak_probe(vb_ctx* c, int32_t kind, int64_t n, int32_t reps, double* out)
   return VB_OK;
 }
 
+int vb_math_probe(vb_ctx* c, int32_t fn, const double* x, int64_t n, double* out, double* out2) {
+  VB_TRY(check_ctx(c));
+  if (!vbk::math_probe_fn_ok(fn)) return fail(VB_EINVAL, "vb_math_probe: unknown helper %d", (int)fn);
+  if (!x || !out || n < 0 || n > ((int64_t)1 << 31)) return fail(VB_EINVAL, "vb_math_probe: null argument or n out of range");
+  In dx;
+  Out dout, dout2;
+  VB_TRY(dx.stage(c, 0, x, (size_t)n));
+  VB_TRY(dout.stage(c, 1, out, (size_t)n));
+  VB_TRY(dout2.stage(c, 2, out2, out2 ? (size_t)n : 0));
+  VB_HIP(vbk::launch_math_probe(fn, dx.d, (long long)n, dout.d, dout2.d, c->stream));
+  VB_TRY(dout.finish(c));
+  VB_TRY(dout2.finish(c));
+  return sync(c);
+}
+
 int vb_run_steps_done(vb_run* r, int64_t* out) {
   if (!r || !out) return fail(VB_EINVAL, "null argument");
   *out = r->done;

@@ -60,7 +60,10 @@ struct Rng {
 
 // ---- fp64 transcendentals for noise generation --------------------------------
 // Box-Muller needs log, sqrt and sin/cos of uniforms only.  These short forms
-// (about 1 ulp) replace the general ocml routines (which carry extra-precision
+// (1-1.9 ulp, each measured against its library form by tests/test_gpu_device_math.py
+// through vb_math_probe; the figures below are the maxima over that test's ~2^18
+// arguments, the library form on the same arguments in brackets) replace the
+// general ocml routines (which carry extra-precision
 // arithmetic and special-case handling the noise path never needs): the
 // transform is ~40% cheaper.  The C oracle uses libm; tests compare at 1e-14.
 
@@ -73,8 +76,33 @@ __device__ __forceinline__ double hfma(double a, double b, double c) {
   return d;
 }
 
+// 1 / d for normal d: v_rcp_f64 seed + two Newton steps: 0.500 ulp, correctly rounded
+// on every argument measured (IEEE division: 0.500).  The reciprocal of
+// the targets (the mixture's posterior weight, 8-schools' 1 / (1 + w)), of log_unit
+// and of the bounds' running mean.
+__device__ __forceinline__ double rcp_refined(double d) {
+  double r = __builtin_amdgcn_rcp(d);
+  r = fma(r, fma(-d, r, 1.0), r);
+  r = fma(r, fma(-d, r, 1.0), r);
+  return r;
+}
+
+// 1 / sqrt(y), y > 0 normal: v_rsq_f64 seed + two Newton steps, 1.87 ulp (1 / sqrt(y)
+// by the library: 1.47) (the adagrad updates'
+// 1 / sqrt(eps + q) and the t draws' 1 / sqrt(gamma) of the mean-field kernels).
+__device__ __forceinline__ double rsqrt_pos(double y) {
+  double r = __builtin_amdgcn_rsq(y);
+  const double hy = 0.5 * y;
+  r = r * fma(-hy * r, r, 1.5);
+  r = r * fma(-hy * r, r, 1.5);
+  return r;
+}
+
 // log(u) for u in (0, 1]: u = m 2^e with m in [sqrt(1/2), sqrt(2)),
 // log m = 2 atanh(f) = 2 f sum_k f^2k / (2k+1), f = (m-1)/(m+1), |f| <= 0.1716.
+// 1.38 ulp (library log: 0.58), the maximum at m ~ sqrt(1/2) where e = -1 and e ln2
+// cancels half of log m; subnormal u and any normal u > 1 included.  (1.71 before
+// den's rounding was carried into f, over the test's bound of library + 1.)
 __device__ __forceinline__ double log_unit(double u) {
   int e;
   double m = frexp(u, &e);
@@ -82,11 +110,13 @@ __device__ __forceinline__ double log_unit(double u) {
   m = lo ? m + m : m;
   e = lo ? e - 1 : e;
   const double num = m - 1.0, den = m + 1.0;
-  double r = __builtin_amdgcn_rcp(den);
-  r = fma(r, fma(-den, r, 1.0), r);
-  r = fma(r, fma(-den, r, 1.0), r);
+  // m + 1 drops m's last bit: dlo = (m + 1) - den exactly (den - 1 is exact), carried
+  // into the residual of f = num / (den + dlo); without it f is off by up to 0.43 ulp
+  // before the polynomial starts
+  const double dlo = m - (den - 1.0);
+  const double r = rcp_refined(den);
   double f = num * r;
-  f = fma(r, fma(-den, f, num), f);
+  f = fma(r, fma(-dlo, f, fma(-den, f, num)), f);
   const double f2 = f * f;
   double p = 0.04347826086956522;            // 1/23
   p = hfma(p, f2, 0.047619047619047616);      // 1/21
@@ -105,8 +135,8 @@ __device__ __forceinline__ double log_unit(double u) {
   return fma(de, 0.6931471805598903, fma(de, 5.497923018708371e-14, t));
 }
 
-// exp(x), ~1 ulp (max 1.07 ulp over 2e7 arguments against a long-double exp; the
-// library form is also ~1 ulp): x = k ln2 + r, |r| <= ln2 / 2, exp(r) = 1 + r +
+// exp(x), 1.00 ulp (library exp: 0.84; subnormal results, in ulps of their spacing,
+// and the reduction ties (k + 1/2) ln2 included): x = k ln2 + r, |r| <= ln2 / 2, exp(r) = 1 + r +
 // r^2 q(r), q of degree 9 fitted on [-ln2/2, ln2/2] (scripts/gen_exp_coef.py), its
 // Horner steps as three-address fmas -- the library's copy each coefficient into a
 // register before a two-address fmac, ~31 instructions against ~23 here.  Overflow
@@ -133,7 +163,7 @@ __device__ __forceinline__ double exp_fast(double x) {
   return x != x ? x : res;
 }
 
-// expm1(x) for 0 <= x <= 700, ~1 ulp: exp_fast's reduction x = k ln2 + r and its
+// expm1(x) for 0 <= x <= 700, 1.71 ulp (library expm1: 1.74): exp_fast's reduction x = k ln2 + r and its
 // polynomial, expm1(r) = r + r^2 q(r) (no cancellation near 0), then
 // 2^k (1 + expm1(r)) - 1 = 2^k expm1(r) + (2^k - 1) in one fma (2^k - 1 exact for
 // k <= 53; larger k round it as 2^k, well within an ulp of the result).  The
@@ -159,15 +189,17 @@ __device__ __forceinline__ double expm1_pos(double x) {
 }
 
 // log1p(w) for w >= 0 finite, without tables: log(1 + w) by log_unit (any positive
-// normal argument) plus the rounding correction of 1 + w; ~1 ulp, ~35
-// instructions against the library's double-double ~100
+// normal argument) plus the rounding correction of 1 + w; ~35 instructions against
+// the library's double-double ~100.  1.70 ulp (library log1p: 1.00) over 1e-320 <= w
+// <= 1e300 (2.24 at w ~ 4e-13 before log_unit carried den's rounding).
 __device__ __forceinline__ double log1p_pos_fast(double w) {
   const double u = 1.0 + w;
   const double corr = (w - (u - 1.0)) * __builtin_amdgcn_rcp(u);
   return log_unit(u) + corr;
 }
 
-// sqrt(y) for y > 0 normal: rsq seed + Goldschmidt refinement.
+// sqrt(y) for y > 0 normal: rsq seed + Goldschmidt refinement.  0.61 ulp (library
+// sqrt, correctly rounded: 0.50).
 __device__ __forceinline__ double sqrt_pos(double y) {
   const double r = __builtin_amdgcn_rsq(y);
   double h = 0.5 * r;
@@ -180,6 +212,7 @@ __device__ __forceinline__ double sqrt_pos(double y) {
 }
 
 // sin(pi x), cos(pi x) for x in [0, 2]: octant reduction + Taylor on [-pi/4, pi/4].
+// Absolute error 1.03 (sin), 0.98 (cos) x 2^-53 (library sinpi 0.82, cospi 0.80).
 __device__ __forceinline__ void sincospi_unit(double x, double& sn, double& cs) {
   const double q = rint(x + x);            // 0..4
   const double r = fma(-0.5, q, x);        // exact, |r| <= 1/4
@@ -216,7 +249,8 @@ __device__ __forceinline__ void sincospi_unit(double x, double& sn, double& cs) 
 // ---- table-driven forms (fused kernel; tables in LDS, vb_tables.hpp) ---------
 // log(u), u in (0, 1]: u = m 2^e, m in [sqrt(1/2), sqrt(2)); c = 1 + i/64 the
 // nearest table point, log m = -log(inv_c) + log1p(m inv_c - 1), |r| < 0.0113,
-// log1p to r^9.  At m ~ 1 the entry is exactly (1, 0): no cancellation.
+// log1p to r^9.  At m ~ 1 the entry is exactly (1, 0): no cancellation.  1.50 ulp
+// (library log: 0.58), every cell edge included.
 __device__ __forceinline__ double log_unit_tab(double u, const double2* ltab) {
   int e;
   double m = frexp(u, &e);
@@ -243,7 +277,8 @@ __device__ __forceinline__ double log_unit_tab(double u, const double2* ltab) {
 
 // log1p(y) for finite y >= 0 (the t family's log(1 + z^2 / df)): u = 1 + y
 // rounded, log1p(y) = log(u) + (y - (u - 1)) / u, the correction (below one ulp
-// of u, relative to u) taken with the hardware reciprocal.
+// of u, relative to u) taken with the hardware reciprocal.  1.52 ulp (library log1p:
+// 1.00).
 __device__ __forceinline__ double log1p_pos_tab(double y, const double2* ltab) {
   const double u = 1.0 + y;
   const double corr = (y - (u - 1.0)) * __builtin_amdgcn_rcp(u);
@@ -251,8 +286,12 @@ __device__ __forceinline__ double log1p_pos_tab(double y, const double2* ltab) {
 }
 
 // log(u) for u in (0, 1) (Box-Muller radius and acceptance uniforms, never 0):
-// u = m 2^e with m in [1/2, 1) and e <= 0, so e ln2, log c and log1p(r) never
-// cancel; c = 1/2 + j/256 the nearest table point, |r| <= 1/256, log1p to r^7.
+// u = m 2^e with m in [1/2, 1) and e <= 0, so e ln2 and log c never cancel; c = 1/2
+// + j/256 the nearest table point, |r| <= 1/256, log1p to r^7.  In the cells just
+// below 1 log c < 0 and log1p(r) > 0 do cancel in part, so the table's log c must
+// carry no rounding of its own: scripts/gen_tables.py picks each inv_c so that
+// -log(inv_c) is within 0.005 ulp of a double.  0.96 ulp (library log: 0.62); 1.95
+// with the nearest-double 1 / c of the earlier table, over the test's bound.
 // The LDS log table holds kBmTab's log rows, then its (0, 1) rows (load_bm_tables); at
 // m ~ 1 the entry is exactly (1, 0).
 __device__ __forceinline__ double log_u01_tab(double u, const double2* ltab) {
@@ -275,7 +314,8 @@ __device__ __forceinline__ double log_u01_tab(double u, const double2* ltab) {
 }
 
 // sin(pi x), cos(pi x) for x in [0, 2]: x = i/128 + r, |r| <= 1/256, table
-// (sin, cos)(pi i / 128) rotated by theta = pi r with short Taylor forms.
+// (sin, cos)(pi i / 128) rotated by theta = pi r with short Taylor forms.  Absolute
+// error 1.34 (sin), 1.31 (cos) x 2^-53 (library 0.85, 0.75); cospi_tab_u24: 1.28.
 __device__ __forceinline__ void sincospi_tab(double x, double& sn, double& cs,
                                              const double2* sct) {
   const double q = rint(x * 128.0);                 // 0..256
@@ -598,9 +638,7 @@ struct Mixture {
     // instead of an IEEE division and the library's double-double log1p, which were
     // most of a row's dependent chain in the block kernel (config 1)
     const double d = 1.0 + e;
-    double r = __builtin_amdgcn_rcp(d);
-    r = fma(r, fma(-d, r, 1.0), r);
-    r = fma(r, fma(-d, r, 1.0), r);
+    const double r = rcp_refined(d);
     const double wb = t > 0.0 ? e * r : r;
     g = -(x + 2.0) + 4.0 * wb;
     return (t > 0.0 ? a : b) + log1p_pos_fast(e) - kLn2;
@@ -761,9 +799,7 @@ struct EightSchools {
     // -2 w / (1 + w) + 1 is NaN at w = inf, as the divided form is)
     const double w = t5 * t5;
     const double dw = 1.0 + w;
-    double rw = __builtin_amdgcn_rcp(dw);
-    rw = fma(rw, fma(-dw, rw, 1.0), rw);
-    rw = fma(rw, fma(-dw, rw, 1.0), rw);
+    const double rw = rcp_refined(dw);
     const double l1 = w < INFINITY ? log1p_pos_fast(w) : w;
     const double gu0 = -2.0 * w * rw + 1.0;
     double lp = h == 0 ? -0.5 * m5 * m5 - l1 + u : 0.0;

@@ -308,6 +308,10 @@ int fr_info(FrWork* W, hipStream_t st, bool* retry = nullptr);
 // n bytes), 2 fp64 MFMA (TFLOP/s), 3 fp64 FMA / 4 u64 multiply VALU issue (G
 // wave-instructions/s; n iterations).
 int probe_rate(int kind, long long n, int reps, hipStream_t st, double* out);
+// Device-math probe (vb_probe.hip): out[i] (out2[i], nullable) = helper fn at x[i].
+bool math_probe_fn_ok(int fn);
+hipError_t launch_math_probe(int fn, const double* x, long long n, double* out, double* out2,
+                             hipStream_t st);
 int fr_warm_save(FrWork* W, hipStream_t st);
 int fr_warm_restore(FrWork* W, hipStream_t st);
 // Clears the Newton-Schulz floor a rerun set (the rerun's own warm steps have

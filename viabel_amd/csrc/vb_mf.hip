@@ -134,15 +134,6 @@ __device__ __forceinline__ double group_bcast(double v, int /*grp*/) {
   }
 }
 
-// 1 / sqrt(y), y > 0: v_rsq_f64 seed + two Newton steps (~1 ulp).
-__device__ __forceinline__ double rsqrt_pos(double y) {
-  double r = __builtin_amdgcn_rsq(y);
-  const double hy = 0.5 * y;
-  r = r * fma(-hy * r, r, 1.5);
-  r = r * fma(-hy * r, r, 1.5);
-  return r;
-}
-
 // PPW column pairs per wavefront (PPW in {1, 2, 4}); pair = wave * PPW + lane / LPP.
 // Owner lanes: quantity / parameter q (0 muA, 1 muB, 2 log sA, 3 log sB) is
 // owned by lane q of the group (PPW >= 2) or by every lane of row q (PPW == 1,

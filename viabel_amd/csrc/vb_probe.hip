@@ -13,7 +13,25 @@
 //                        SIMD; G wave-instructions/s (the VALU issue peak the
 //                        fp64 kernels are priced against)
 //   kind 4  u64 multiply v_mad_u64_u32 chains (Philox's multiply), as kind 3
+//
+// and the device-math probe (vb_math_probe; test support for
+// tests/test_gpu_device_math.py): one thread per argument calls the same vbd::
+// inline function the kernels call -- the table forms on LDS tables filled by the
+// kernels' own load_bm_tables -- or its library counterpart, the measuring stick.
+//
+//   fn  0 exp_fast       1 expm1_pos        2 log_unit      3 log1p_pos_fast
+//       4 sqrt_pos       5 sincospi_unit    6 log_unit_tab  7 log1p_pos_tab
+//       8 log_u01_tab    9 sincospi_tab    10 cospi_tab_u24 (argument: the integer b
+//      11 rcp_refined   12 rsqrt_pos           as a double)
+//      16 exp  17 expm1  18 log  19 log1p  20 sqrt  21 sinpi / cospi  22 1 / x
+//      23 1 / sqrt(x)   (library forms)
+//
+// sin goes to out and cos to out2 (5, 9, 21); 10 writes cos to out.  The table
+// forms index LDS by their argument, so an argument outside a form's domain (8: 0 <
+// u < 1; 9: 0 <= x <= 2; 10: an integer in [0, 2^24)) is answered with NaN and the
+// form is not called.
 #include "../../include/viabel_amd.h"
+#include "vb_device.hpp"
 #include "vb_internal.hpp"
 
 #include <hip/hip_runtime.h>
@@ -110,7 +128,68 @@ __global__ __launch_bounds__(256) void probe_mad64_kernel(double* out, int iters
   out[blockIdx.x * 256 + threadIdx.x] = (double)(s & 0xFFFF);
 }
 
+__global__ __launch_bounds__(256) void math_probe_kernel(int fn, const double* __restrict__ x,
+                                                         long long n, double* __restrict__ out,
+                                                         double* __restrict__ out2) {
+  using namespace vbd;
+  __shared__ double2 s_sct[kSinCosN];
+  __shared__ double2 s_lt[kLogN + kLogU01N];
+  load_bm_tables(s_sct, s_lt);
+  __syncthreads();
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double a = x[i];
+  const double nan = __longlong_as_double(0x7FF8000000000000LL);
+  double r = nan, r2 = nan;
+  switch (fn) {
+    case 0: r = exp_fast(a); break;
+    case 1: r = expm1_pos(a); break;
+    case 2: r = log_unit(a); break;
+    case 3: r = log1p_pos_fast(a); break;
+    case 4: r = sqrt_pos(a); break;
+    case 5: sincospi_unit(a, r, r2); break;
+    case 6: r = log_unit_tab(a, s_lt); break;
+    case 7: r = log1p_pos_tab(a, s_lt); break;
+    case 8:
+      if (a > 0.0 && a < 1.0) r = log_u01_tab(a, s_lt);
+      break;
+    case 9:
+      if (a >= 0.0 && a <= 2.0) sincospi_tab(a, r, r2, s_sct);
+      break;
+    case 10:
+      if (a >= 0.0 && a < 16777216.0 && a == rint(a)) r = cospi_tab_u24((uint32_t)a, s_sct);
+      break;
+    case 11: r = rcp_refined(a); break;
+    case 12: r = rsqrt_pos(a); break;
+    case 16: r = exp(a); break;
+    case 17: r = expm1(a); break;
+    case 18: r = log(a); break;
+    case 19: r = log1p(a); break;
+    case 20: r = sqrt(a); break;
+    case 21:
+      r = sinpi(a);
+      r2 = cospi(a);
+      break;
+    case 22: r = 1.0 / a; break;
+    case 23: r = 1.0 / sqrt(a); break;
+    default: break;
+  }
+  out[i] = r;
+  if (out2) out2[i] = r2;
+}
+
 }  // namespace
+
+bool math_probe_fn_ok(int fn) { return (fn >= 0 && fn <= 12) || (fn >= 16 && fn <= 23); }
+
+// out[i] (and out2[i], nullable) = helper fn at x[i]; device pointers
+hipError_t launch_math_probe(int fn, const double* x, long long n, double* out, double* out2,
+                             hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(math_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, fn, x, n,
+                     out, out2);
+  return hipGetLastError();
+}
 
 // rate of one probe (see the file header), best of `reps` timed launches after
 // one untimed launch; buffers are allocated and freed here
