@@ -922,12 +922,17 @@ static size_t radix_temp_bytes(long long cap) {
 
 static long long cap_of(long long cap) { return cap < kTailMax ? kTailMax : cap; }
 
+// capacity of each quadrature array (bs, ks, L, w): the fit of n <= cap values
+// uses m = 30 + floor(sqrt(n)) points (psis.py:268); one spare slot
+static long long quad_cap(long long cap) { return 30 + (long long)std::sqrt((double)cap) + 1; }
+
 size_t psis_scratch_bytes(long long tail_cap) {
   const long long cap = cap_of(tail_cap);
   // state + partials + radix hist + tail (value, index) x2 + y + grid arrays + sort temp
   return 256 + sizeof(double) * kPsisBlocks * 2 + sizeof(unsigned) * kSelBins +
          sizeof(unsigned) * kPsisBlocks + 2 * cap * (sizeof(double) + sizeof(long long)) +
-         sizeof(double) * cap + sizeof(double) * 8 * 256 + radix_temp_bytes(tail_cap) + 256;
+         sizeof(double) * cap + sizeof(double) * 4 * quad_cap(cap) + radix_temp_bytes(tail_cap) +
+         256;
 }
 
 struct PsisScratch {
@@ -969,10 +974,11 @@ static PsisScratch carve(void* base, long long tail_cap) {
   p += sizeof(long long) * kTailMax;
   s.y = reinterpret_cast<double*>(p);
   p += sizeof(double) * kTailMax;
+  const long long mq = quad_cap(kTailMax);   // m <= mq - 1 points for any n <= capacity
   s.bs = reinterpret_cast<double*>(p);
-  s.ks = s.bs + 256;
-  s.Lw = s.ks + 256;
-  p += sizeof(double) * 8 * 256;
+  s.ks = s.bs + mq;
+  s.Lw = s.ks + mq;   // L[m] then w[m] (gpd_final_kernel): 2 mq doubles
+  p += sizeof(double) * 4 * mq;
   p = reinterpret_cast<unsigned char*>((reinterpret_cast<uintptr_t>(p) + 255) & ~uintptr_t(255));
   s.sort_tmp = p;
   s.sort_bytes = radix_temp_bytes(tail_cap);
