@@ -516,11 +516,8 @@ bool predraw_overlap_streams(vb_ctx* c) {
   return true;
 }
 
-struct FamInfo {
-  int kind;
-  int D;
+struct FamInfo : vbk::Family {
   size_t P;  // length of lambda
-  double df, t_scale, shape, t_const;
 };
 
 int check_family(const vb_family* f, FamInfo* o) {
@@ -616,15 +613,19 @@ int check_target(const vb_target* t, int D, vbk::GlmHead* glm = nullptr) {
   return VB_OK;
 }
 
-// the kinds that always take the materialised path (no block / rows kernel)
-bool materialised_target(int kind) {
-  return kind == VB_TARGET_CALLBACK || kind == VB_TARGET_REGRESSION;
+// The launch functions' view of a vb_noise: eps is the device copy of its host draws
+// (null: Philox); a stream_stride of 0 means 1.
+vbk::Noise noise_of(const vb_noise* n, const double* eps) {
+  return vbk::Noise{eps, (uint32_t)(n->seed & 0xffffffffu), (uint32_t)(n->seed >> 32), n->stream,
+                    n->stream_stride ? n->stream_stride : 1u, (long long)n->step};
 }
 
-void key_of(uint64_t seed, uint32_t* k0, uint32_t* k1) {
-  *k0 = (uint32_t)(seed & 0xffffffffu);
-  *k1 = (uint32_t)(seed >> 32);
-}
+// Context slots that target_params stages into.  Each stays clear of the slots its
+// entry points stage arguments and scratch in:
+constexpr int kSlotRunTparams = 1;  // vb_run_create: copied into the run; init then takes 0
+constexpr int kSlotTparams = 3;     // corr_gauss: lam, draws, gradient in 0-2, the value in 4
+constexpr int kSlotTparamsLw = 4;   // corr_gauss in vb_log_weights, whose samples take 3
+constexpr int kSlotGlm = 8;         // regression block: the mean-field calls use all of 0-7
 
 // Device copy of a target's parameters and its scalar log normaliser.
 int target_params(vb_ctx* c, int s, const vb_target* t, const double** dev, double* tconst) {
@@ -653,9 +654,49 @@ int fr_work(vb_ctx* c, vbk::FrWork** w) {
   return VB_OK;
 }
 
-int require_fr(int fam_kind, int tgt_kind) {
+// The four implementations of a value-and-gradient step, a run or a log-weight call
+// ("The path and the boundary", has the table this implements).
+enum class Path {
+  ColumnPair,    // fused kernel over column pairs: separable targets at D > kBlockDMax
+  Block,         // one workgroup per problem: D <= kBlockDMax
+  Materialised,  // mean-field x [N][D] in HBM, one value_grad + update per step (mf_wide_*)
+  FullRank,      // the full-rank t family (fr_*)
+};
+
+// What decides the path.  A caller leaves out what it does not have: log weights
+// have no objective, and a single value-and-gradient call has no optimiser, window
+// or problem count.
+struct PathFacts {
+  int fam, tgt, D;
+  int obj = VB_OBJ_KLVI;
+  int opt = VB_OPT_ADAGRAD;
+  int window = 1;
+  long long nprob = 1;
+};
+
+int check_pairing(int fam_kind, int tgt_kind) {
   if (tgt_kind == VB_TARGET_CORR_GAUSS && fam_kind != VB_FAMILY_FR_T)
     return fail(VB_EUNSUPPORTED, "the corr_gauss target is implemented for the full-rank family only");
+  return VB_OK;
+}
+
+int choose_path(const PathFacts& f, Path* out) {
+  VB_TRY(check_pairing(f.fam, f.tgt));
+  if (f.fam == VB_FAMILY_FR_T) {
+    *out = Path::FullRank;
+    return VB_OK;
+  }
+  const bool wide = f.D > vbk::kBlockDMax;
+  // CHIVI's weights couple all coordinates of a sample: no column-pair kernel
+  const bool pairs = wide && vbk::target_separable(f.tgt) && f.obj != VB_OBJ_CHIVI;
+  // the column-pair kernel has adagrad only, and both fused kernels keep its window
+  // on chip (<= 64 steps); host callbacks and regression blocks have no fused kernel
+  const bool ia = f.opt != VB_OPT_ADAGRAD;
+  const bool materialised = f.tgt == VB_TARGET_CALLBACK || f.tgt == VB_TARGET_REGRESSION ||
+                            (wide && (!pairs || ia)) || (!ia && f.window > 64);
+  if (pairs && f.nprob != 1)
+    return fail(VB_EUNSUPPORTED, "wide (D > %d) runs hold one problem per vb_run", vbk::kBlockDMax);
+  *out = materialised ? Path::Materialised : pairs ? Path::ColumnPair : Path::Block;
   return VB_OK;
 }
 
@@ -668,22 +709,29 @@ vbk::HostTarget host_of(const vb_target* t) {
   return h;
 }
 
-vbk::FrSpec fr_spec(const FamInfo& fi, const vb_target* tgt, const vb_objective* obj,
+// obj null: log weights (no sample count, no objective flags)
+vbk::Spec make_spec(const FamInfo& fi, const vb_target* tgt, const vb_objective* obj,
                     const double* tparams, double tconst, const vbk::GlmHead& glm) {
-  vbk::FrSpec f{};
-  f.glm = glm;
-  f.host = host_of(tgt);
-  f.D = fi.D;
-  f.N = (int)obj->n_samples;
+  vbk::Spec f{};
+  f.fam = fi;
+  f.N = obj ? (int)obj->n_samples : 0;
   f.tgt = tgt->kind;
-  f.chivi = obj->kind == VB_OBJ_CHIVI;
-  f.pd = obj->kind == VB_OBJ_KLVI_PD;
-  f.df = fi.df;
-  f.t_const = fi.t_const;
-  f.alpha = obj->alpha;
+  f.chivi = obj && obj->kind == VB_OBJ_CHIVI;
+  f.pd = obj && obj->kind == VB_OBJ_KLVI_PD;
+  f.alpha = obj ? obj->alpha : 2.0;
   f.tparams = tparams;
   f.tconst = tconst;
+  f.host = host_of(tgt);
+  f.glm = glm;
   return f;
+}
+
+int check_objective(const vb_objective* obj) {
+  if (obj->n_samples < 1 || obj->n_samples > (1LL << 31))
+    return fail(VB_EINVAL, "n_samples must be positive");
+  if (obj->kind < VB_OBJ_KLVI || obj->kind > VB_OBJ_KLVI_PD)
+    return fail(VB_EINVAL, "unknown objective %d", obj->kind);
+  return VB_OK;
 }
 
 // Constant of the column-pair kernel's value: KLVI -(c0 + sum log s + mean log p);
@@ -693,26 +741,6 @@ double sep_c0(const FamInfo& fi, bool pd) {
   const double D = (double)fi.D;
   if (fi.kind == VB_FAMILY_MF_T) return pd ? -D * fi.t_const : 0.0;
   return pd ? 0.5 * D * std::log(2 * M_PI) : 0.5 * D * (1.0 + std::log(2 * M_PI));
-}
-
-vbk::MfSpec mf_spec(const FamInfo& fi, const vb_target* tgt, const vb_objective* obj,
-                    const double* tparams, const vbk::GlmHead& glm) {
-  vbk::MfSpec f{};
-  f.tparams = tparams;
-  f.glm = glm;
-  f.host = host_of(tgt);
-  f.fam = fi.kind;
-  f.D = fi.D;
-  f.N = obj ? (int)obj->n_samples : 0;
-  f.tgt = tgt->kind;
-  f.chivi = obj && obj->kind == VB_OBJ_CHIVI;
-  f.pd = obj && obj->kind == VB_OBJ_KLVI_PD;
-  f.alpha = obj ? obj->alpha : 2.0;
-  f.t_scale = fi.t_scale;
-  f.shape = fi.shape;
-  f.df = fi.df;
-  f.t_const = fi.t_const;
-  return f;
 }
 
 // vb_objective_value_grad for the full-rank t family
@@ -729,17 +757,16 @@ int fr_objective(vb_ctx* c, const FamInfo& fi, const vb_target* tgt, const vb_ob
   VB_TRY(dg.stage(c, 2, grad, fi.P));
   const double* tp;
   double tc;
-  VB_TRY(target_params(c, tgt->kind == VB_TARGET_REGRESSION ? 8 : 3, tgt, &tp, &tc));
+  VB_TRY(target_params(c, tgt->kind == VB_TARGET_REGRESSION ? kSlotGlm : kSlotTparams, tgt, &tp,
+                       &tc));
   VB_TRY(c->slot[4].reserve(sizeof(double) * 2));
-  uint32_t k0, k1;
-  key_of(noise->seed, &k0, &k1);
   vbk::FrWork* W;
   VB_TRY(fr_work(c, &W));
   // a root or gradient solve that needed more iterations than launched (an
   // ill-conditioned Sigma) runs the call again with larger counts (fr_info)
   for (int attempt = 0;; ++attempt) {
-    VB_TRY(vbk::fr_value_grad(W, fr_spec(fi, tgt, obj, tp, tc, glm), dl.d, host ? dn.d : nullptr, k0,
-                              k1, noise->stream, (uint32_t)noise->step, c->slot[4].d(), dg.d,
+    VB_TRY(vbk::fr_value_grad(W, make_spec(fi, tgt, obj, tp, tc, glm), dl.d,
+                              noise_of(noise, host ? dn.d : nullptr), c->slot[4].d(), dg.d,
                               c->stream));
     VB_TRY(sync(c));
     bool again = false;
@@ -766,6 +793,47 @@ vbk::LrSched make_sched(long long n, double lr, double lr_end) {
     s.end = (3 * n) / 4;
   }
   return s;
+}
+
+// The part of the fused kernels' arguments that a single value-and-gradient call and
+// a run share: shape, family constants, objective flags, noise.  The caller adds the
+// window, the step range, emit_grad, its buffers and the schedule.
+vbk::SepArgs sep_args(const FamInfo& fi, int N, int obj, const vbk::Noise& nz) {
+  vbk::SepArgs a{};
+  a.D = fi.D;
+  a.N = N;
+  a.n_pairs = a.n_waves = (fi.D + 1) / 2;
+  a.pd = obj == VB_OBJ_KLVI_PD ? (fi.kind == VB_FAMILY_MF_T ? 2 : 1) : 0;
+  a.rng_step0 = nz.step;
+  a.t_scale = fi.t_scale;
+  a.shape = fi.shape;
+  a.noise = nz.eps;
+  a.k0 = nz.k0;
+  a.k1 = nz.k1;
+  a.stream = nz.stream;
+  return a;
+}
+
+vbk::BlockArgs block_args(const FamInfo& fi, int N, int obj, double alpha, const vbk::Noise& nz) {
+  vbk::BlockArgs a{};
+  a.pf = block_pf_enabled();
+  a.D = fi.D;
+  a.N = N;
+  a.P = (int)fi.P;
+  a.chivi = obj == VB_OBJ_CHIVI;
+  a.pd = obj == VB_OBJ_KLVI_PD;
+  a.rng_step0 = nz.step;
+  a.alpha = alpha;
+  a.t_scale = fi.t_scale;
+  a.shape = fi.shape;
+  a.t_const = fi.t_const;
+  a.df = fi.df;
+  a.noise = nz.eps;
+  a.k0 = nz.k0;
+  a.k1 = nz.k1;
+  a.stream = nz.stream;
+  a.stream_stride = nz.stride;
+  return a;
 }
 
 }  // namespace
@@ -848,14 +916,11 @@ int vb_family_sample(vb_ctx* c, const vb_family* fam, const double* lam, int64_t
     VB_TRY(dl.stage(c, 0, lam, fi.P));
     if (host) VB_TRY(dn.stage(c, 1, noise->eps, nd + n));
     VB_TRY(dx.stage(c, 2, x_out, nd));
-    uint32_t k0, k1;
-    key_of(noise->seed, &k0, &k1);
     vbk::FrWork* W;
     VB_TRY(fr_work(c, &W));
     VB_TRY(vbk::fr_sqrt(W, fi.D, dl.d, c->stream));
     const double *s, *z;
-    VB_TRY(vbk::fr_draw(W, fi.D, n, fi.df, host ? dn.d : nullptr, k0, k1, noise->stream,
-                        (uint32_t)noise->step, &s, &z, c->stream));
+    VB_TRY(vbk::fr_draw(W, fi, n, noise_of(noise, host ? dn.d : nullptr), &s, &z, c->stream));
     VB_TRY(vbk::fr_transform(W, fi.D, n, dl.d, s, z, dx.d, c->stream));
     VB_TRY(dx.finish(c));
     return sync(c);
@@ -869,11 +934,9 @@ int vb_family_sample(vb_ctx* c, const vb_family* fam, const double* lam, int64_t
     VB_TRY(dn.stage(c, 1, noise->eps, nd));
   }
   VB_TRY(dx.stage(c, 2, x_out, nd));
-  uint32_t k0, k1;
-  key_of(noise->seed, &k0, &k1);
-  VB_HIP(vbk::launch_sample(fi.kind, fi.D, n, dl.d, fi.t_scale, fi.shape,
-                            noise->kind == VB_NOISE_HOST ? dn.d : nullptr, k0, k1, noise->stream,
-                            (uint32_t)noise->step, dx.d, c->stream));
+  VB_HIP(vbk::launch_sample(fi, n, dl.d,
+                            noise_of(noise, noise->kind == VB_NOISE_HOST ? dn.d : nullptr), dx.d,
+                            c->stream));
   VB_TRY(dx.finish(c));
   return sync(c);
 }
@@ -893,15 +956,14 @@ int vb_family_logdensity(vb_ctx* c, const vb_family* fam, const double* lam, con
     VB_TRY(dout.stage(c, 2, out, (size_t)n));
     vbk::FrWork* W;
     VB_TRY(fr_work(c, &W));
-    VB_TRY(vbk::fr_logdensity(W, fi.D, fi.df, fi.t_const, dl.d, dxx.d, n, dout.d, c->stream));
+    VB_TRY(vbk::fr_logdensity(W, fi, dl.d, dxx.d, n, dout.d, c->stream));
     VB_TRY(dout.finish(c));
     return sync(c);
   }
   VB_TRY(dl.stage(c, 0, lam, 2 * (size_t)fi.D));
   VB_TRY(dxx.stage(c, 1, x, (size_t)n * fi.D));
   VB_TRY(dout.stage(c, 2, out, (size_t)n));
-  VB_HIP(vbk::launch_family_logdensity(fi.kind, fi.D, n, dl.d, fi.df, fi.t_const, dxx.d, dout.d,
-                                       c->stream));
+  VB_HIP(vbk::launch_family_logdensity(fi, n, dl.d, dxx.d, dout.d, c->stream));
   VB_TRY(dout.finish(c));
   return sync(c);
 }
@@ -954,7 +1016,7 @@ int vb_target_logdensity(vb_ctx* c, const vb_target* tgt, const double* x, int64
     if (n == 0) return VB_OK;
     const double* tp;
     double tc;
-    VB_TRY(target_params(c, 8, tgt, &tp, &tc));
+    VB_TRY(target_params(c, kSlotGlm, tgt, &tp, &tc));
     vbk::FrWork* W;
     VB_TRY(fr_work(c, &W));
     VB_TRY(vbk::glm_target_eval(W, glm, D, n, tp, dxx.d, dout.d, dg.d, c->stream));
@@ -962,7 +1024,7 @@ int vb_target_logdensity(vb_ctx* c, const vb_target* tgt, const double* x, int64
     if (n == 0) return VB_OK;
     const double* tp;
     double tc;
-    VB_TRY(target_params(c, 3, tgt, &tp, &tc));
+    VB_TRY(target_params(c, kSlotTparams, tgt, &tp, &tc));
     vbk::FrWork* W;
     VB_TRY(fr_work(c, &W));
     VB_TRY(vbk::fr_target(W, tgt->kind, D, n, tp, tc, dxx.d, dout.d, dg.d, c->stream));
@@ -984,20 +1046,16 @@ int vb_objective_value_grad(vb_ctx* c, const vb_family* fam, const vb_target* tg
   vbk::GlmHead glm{};
   VB_TRY(check_target(tgt, fi.D, &glm));
   if (!obj || !lam || !noise || !value || !grad) return fail(VB_EINVAL, "null argument");
-  if (obj->n_samples < 1 || obj->n_samples > (1LL << 31))
-    return fail(VB_EINVAL, "n_samples must be positive");
-  if (obj->kind < VB_OBJ_KLVI || obj->kind > VB_OBJ_KLVI_PD)
-    return fail(VB_EINVAL, "unknown objective %d", obj->kind);
+  VB_TRY(check_objective(obj));
   if (obj->kind == VB_OBJ_CHIVI && !(obj->alpha > 0))
     return fail(VB_EINVAL, "alpha must be positive");
-  VB_TRY(require_fr(fi.kind, tgt->kind));
-  if (fi.kind == VB_FAMILY_FR_T) return fr_objective(c, fi, tgt, obj, lam, noise, value, grad, glm);
+  Path path;
+  VB_TRY(choose_path({fi.kind, tgt->kind, fi.D, obj->kind}, &path));
+  if (path == Path::FullRank) return fr_objective(c, fi, tgt, obj, lam, noise, value, grad, glm);
   const int D = fi.D, N = (int)obj->n_samples;
   const size_t P = 2 * (size_t)D;
   const bool host = noise->kind == VB_NOISE_HOST;
   if (host && !noise->eps) return fail(VB_EINVAL, "host noise requires eps");
-  uint32_t k0, k1;
-  key_of(noise->seed, &k0, &k1);
   In dl, dn;
   Out dg;
   VB_TRY(dl.stage(c, 0, lam, P));
@@ -1009,88 +1067,61 @@ int vb_objective_value_grad(vb_ctx* c, const vb_family* fam, const vb_target* tg
   double* dval;
   VB_TRY(c->slot[4].reserve(sizeof(double) * 2));
   dval = c->slot[4].d();
+  const vbk::Noise nz = noise_of(noise, host ? dn.d : nullptr);
 
-  const bool pd = obj->kind == VB_OBJ_KLVI_PD;
-  const bool sep = vbk::target_separable(tgt->kind) && obj->kind != VB_OBJ_CHIVI;
-  const bool cb = materialised_target(tgt->kind);
-  if (sep && D > vbk::kBlockDMax) {
-    vbk::SepArgs a{};
-    a.D = D;
-    a.N = N;
-    a.W = 1;
-    a.n_pairs = (D + 1) / 2;
-    a.n_steps = 1;
-    a.emit_grad = 1;
-    a.pd = pd ? (fi.kind == VB_FAMILY_MF_T ? 2 : 1) : 0;
-    a.step0 = 0;
-    a.hist_start = 1LL << 62;
-    a.rng_step0 = (long long)noise->step;
-    a.n_waves = a.n_pairs;
-    a.t_scale = fi.t_scale;
-    a.shape = fi.shape;
-    a.lam = c->slot[3].d();
-    VB_TRY(c->slot[5].reserve(sizeof(double) * a.n_waves));
-    a.vpart = c->slot[5].d();
-    a.grad = dg.d;
-    a.noise = host ? dn.d : nullptr;
-    a.k0 = k0;
-    a.k1 = k1;
-    a.stream = noise->stream;
-    VB_HIP(vbk::launch_sep(fi.kind, tgt->kind, host, a, c->stream));
-    VB_HIP(vbk::launch_sep_values(a.vpart, 1, a.n_waves, sep_c0(fi, pd), dval, c->stream));
-  } else if (D <= vbk::kBlockDMax && !cb) {
-    vbk::BlockArgs a{};
-    a.pf = block_pf_enabled();
-    a.D = D;
-    a.N = N;
-    a.W = 1;
-    a.P = (int)P;
-    a.n_steps = 1;
-    a.emit_grad = 1;
-    a.chivi = obj->kind == VB_OBJ_CHIVI;
-    a.pd = pd;
-    a.step0 = 0;
-    a.hist_start = 1LL << 62;
-    a.n_iters = 1;
-    a.n_hist = 0;
-    a.rng_step0 = (long long)noise->step;
-    a.alpha = obj->alpha;
-    a.t_scale = fi.t_scale;
-    a.shape = fi.shape;
-    a.t_const = fi.t_const;
-    a.df = fi.df;
-    a.lam = c->slot[3].d();
-    a.ring = nullptr;
-    a.values = dval;
-    a.grad = dg.d;
-    a.noise = host ? dn.d : nullptr;
-    a.k0 = k0;
-    a.k1 = k1;
-    a.stream = noise->stream;
-    a.stream_stride = 1;
-    if (!host && predraw_enabled(fi.kind)) {
-      const bool need_lq = a.chivi || a.pd;
-      VB_TRY(c->slot[6].reserve(sizeof(double) * (size_t)N * D));
-      if (need_lq) VB_TRY(c->slot[7].reserve(sizeof(double) * (size_t)N));
-      VB_HIP(vbk::launch_block_predraw(fi.kind, D, N, 1, 1, k0, k1, a.stream, 1, a.rng_step0,
-                                       fi.t_scale, fi.shape, fi.df, fi.t_const, c->slot[6].d(),
-                                       need_lq ? c->slot[7].d() : nullptr, c->stream));
-      a.noise = c->slot[6].d();
-      a.noise_lq = need_lq ? c->slot[7].d() : nullptr;
-      VB_HIP(vbk::launch_block(fi.kind, tgt->kind, true, a, 1, c->stream));
-    } else {
-      VB_HIP(vbk::launch_block(fi.kind, tgt->kind, host, a, 1, c->stream));
+  switch (path) {
+    case Path::ColumnPair: {
+      vbk::SepArgs a = sep_args(fi, N, obj->kind, nz);
+      a.W = 1;
+      a.n_steps = 1;
+      a.emit_grad = 1;
+      a.step0 = 0;
+      a.hist_start = 1LL << 62;
+      a.lam = c->slot[3].d();
+      VB_TRY(c->slot[5].reserve(sizeof(double) * a.n_waves));
+      a.vpart = c->slot[5].d();
+      a.grad = dg.d;
+      VB_HIP(vbk::launch_sep(fi.kind, tgt->kind, host, a, c->stream));
+      VB_HIP(vbk::launch_sep_values(a.vpart, 1, a.n_waves, sep_c0(fi, a.pd != 0), dval, c->stream));
+      break;
     }
-  } else {
-    // CHIVI or a non-separable target at D > kBlockDMax: materialised path
-    const double* tp;
-    double tc;
-    VB_TRY(target_params(c, 8, tgt, &tp, &tc));
-    vbk::FrWork* W;
-    VB_TRY(fr_work(c, &W));
-    VB_TRY(vbk::mf_wide_value_grad(W, mf_spec(fi, tgt, obj, tp, glm), c->slot[3].d(), host ? dn.d : nullptr,
-                                   k0, k1, noise->stream, (uint32_t)noise->step, dval, dg.d,
-                                   c->stream));
+    case Path::Block: {
+      vbk::BlockArgs a = block_args(fi, N, obj->kind, obj->alpha, nz);
+      a.W = 1;
+      a.n_steps = 1;
+      a.emit_grad = 1;
+      a.step0 = 0;
+      a.hist_start = 1LL << 62;
+      a.n_iters = 1;
+      a.n_hist = 0;
+      a.lam = c->slot[3].d();
+      a.ring = nullptr;
+      a.values = dval;
+      a.grad = dg.d;
+      if (!host && predraw_enabled(fi.kind)) {
+        const bool need_lq = a.chivi || a.pd;
+        VB_TRY(c->slot[6].reserve(sizeof(double) * (size_t)N * D));
+        if (need_lq) VB_TRY(c->slot[7].reserve(sizeof(double) * (size_t)N));
+        VB_HIP(vbk::launch_block_predraw(fi, N, 1, 1, nz, c->slot[6].d(),
+                                         need_lq ? c->slot[7].d() : nullptr, c->stream));
+        a.noise = c->slot[6].d();
+        a.noise_lq = need_lq ? c->slot[7].d() : nullptr;
+        VB_HIP(vbk::launch_block(fi.kind, tgt->kind, true, a, 1, c->stream));
+      } else {
+        VB_HIP(vbk::launch_block(fi.kind, tgt->kind, host, a, 1, c->stream));
+      }
+      break;
+    }
+    default: {
+      // CHIVI or a non-separable target at D > kBlockDMax, a callback or a regression block
+      const double* tp;
+      double tc;
+      VB_TRY(target_params(c, kSlotGlm, tgt, &tp, &tc));
+      vbk::FrWork* W;
+      VB_TRY(fr_work(c, &W));
+      VB_TRY(vbk::mf_wide_value_grad(W, make_spec(fi, tgt, obj, tp, tc, glm), c->slot[3].d(), nz, dval,
+                                     dg.d, c->stream));
+    }
   }
   VB_HIP(hipMemcpyAsync(value, dval, sizeof(double), hipMemcpyDeviceToHost, c->stream));
   VB_TRY(dg.finish(c));
@@ -1110,16 +1141,14 @@ struct vb_run {
   double eps = 0.1;
   vbk::LrSched sched{};
   int opt = 0;  // vb_optimizer_kind
-  bool sep = false;
+  Path path = Path::Block;  // choose_path's answer for this run
   int n_waves = 0;
   int max_chunk = 256;
   DevBuf lam, ring, hist, values, vpart, noise, smooth;
   DevBuf noise_lq;  // pre-drawn log q partials (block kernel, predraw)
   DevBuf noise2, noise_lq2;  // the second chunk buffer of the overlapped pre-draw
-  // full-rank family / wide mean-field: one value_grad + update per step
-  bool fr = false, wide = false;
-  vbk::FrSpec spec{};
-  vbk::MfSpec mspec{};
+  // full-rank family / materialised mean-field: one value_grad + update per step
+  vbk::Spec spec{};
   DevBuf tparams, grad;
   DevBuf backup;  // full rank: lambda and the adagrad window at the start of an advance
   long long fr_retries = 0;  // full rank: advances run again after a short warm root
@@ -1165,7 +1194,7 @@ int vb_run_create(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const v
   VB_TRY(check_family(fam, &fi));
   vbk::GlmHead glm{};
   VB_TRY(check_target(tgt, fi.D, &glm));
-  VB_TRY(require_fr(fi.kind, tgt->kind));
+  VB_TRY(check_pairing(fi.kind, tgt->kind));  // reported before the argument errors below
   if (!obj || !cfg || !init) return fail(VB_EINVAL, "null argument");
   if (!(cfg->learning_rate > 0)) return fail(VB_EINVAL, "learning rate must be positive");
   if (!std::isnan(cfg->learning_rate_end) && cfg->learning_rate <= cfg->learning_rate_end)
@@ -1176,23 +1205,11 @@ int vb_run_create(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const v
   if (cfg->window < 1) return fail(VB_EINVAL, "window must be positive");
   if (cfg->n_iters < 0) return fail(VB_EINVAL, "n_iters must be non-negative");
   if (n_problems < 1) return fail(VB_EINVAL, "n_problems must be positive");
-  if (obj->n_samples < 1 || obj->n_samples > (1LL << 31))
-    return fail(VB_EINVAL, "n_samples must be positive");
-  const int D = fi.D;
-  const bool fr = fi.kind == VB_FAMILY_FR_T;
-  if (obj->kind < VB_OBJ_KLVI || obj->kind > VB_OBJ_KLVI_PD)
-    return fail(VB_EINVAL, "unknown objective %d", obj->kind);
-  const bool sep = !fr && vbk::target_separable(tgt->kind) && obj->kind != VB_OBJ_CHIVI &&
-                   (D > vbk::kBlockDMax);
-  // D > kBlockDMax without the fused kernel (CHIVI, non-separable targets, IA
-  // optimisers): the materialised mean-field path, one problem per run
-  // (the fused kernels keep the adagrad window on chip: windows > 64 use the
-  // materialised path, whose window lives in HBM)
-  const bool big_window = !ia && cfg->window > 64;
-  const bool wide = !fr && ((D > vbk::kBlockDMax && (!sep || ia)) ||
-                            materialised_target(tgt->kind) || big_window);
-  if (sep && n_problems != 1)
-    return fail(VB_EUNSUPPORTED, "wide (D > %d) runs hold one problem per vb_run", vbk::kBlockDMax);
+  VB_TRY(check_objective(obj));
+  Path path;
+  VB_TRY(choose_path({fi.kind, tgt->kind, fi.D, obj->kind, cfg->optimizer, cfg->window, n_problems},
+                     &path));
+  const bool fr = path == Path::FullRank, wide = path == Path::Materialised;
 
   vb_run* r = new (std::nothrow) vb_run();
   if (!r) return fail(VB_ENOMEM, "out of host memory");
@@ -1215,9 +1232,8 @@ int vb_run_create(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const v
   }
   r->eps = cfg->epsilon;
   r->sched = make_sched(cfg->n_iters, cfg->learning_rate, cfg->learning_rate_end);
-  r->sep = sep && !wide;
-  r->wide = wide;
-  r->n_waves = (D + 1) / 2;
+  r->path = path;
+  r->n_waves = (fi.D + 1) / 2;
   const size_t P = fi.P;
   auto bail = [&](int rc) {
     delete r;
@@ -1230,7 +1246,7 @@ int vb_run_create(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const v
   double tc = 0.0;
   if (fr || (wide && tgt->kind == VB_TARGET_REGRESSION)) {
     const double* tp;
-    if ((rc = target_params(c, 1, tgt, &tp, &tc)) != VB_OK) return bail(rc);
+    if ((rc = target_params(c, kSlotRunTparams, tgt, &tp, &tc)) != VB_OK) return bail(rc);
     run_tp = tp;
     if (tp) {
       const size_t np = (size_t)tgt->n_params;
@@ -1241,13 +1257,8 @@ int vb_run_create(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const v
       run_tp = r->tparams.d();
     }
   }
-  if (wide) {
-    if ((rc = r->grad.reserve(sizeof(double) * P)) != VB_OK) return bail(rc);
-    r->mspec = mf_spec(fi, tgt, obj, run_tp, glm);
-  }
-  if (fr) {
-    r->fr = true;
-    r->spec = fr_spec(fi, tgt, obj, run_tp, tc, glm);
+  if (fr || wide) {
+    r->spec = make_spec(fi, tgt, obj, run_tp, tc, glm);
     if ((rc = r->grad.reserve(sizeof(double) * P)) != VB_OK) return bail(rc);
   }
   if ((rc = r->lam.reserve(sizeof(double) * P * n_problems)) != VB_OK) return bail(rc);
@@ -1257,7 +1268,8 @@ int vb_run_create(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const v
   if ((rc = r->values.reserve(sizeof(double) * std::max<long long>(r->n_iters, 1) * n_problems)) != VB_OK)
     return bail(rc);
   if ((rc = r->smooth.reserve(sizeof(double) * P * n_problems)) != VB_OK) return bail(rc);
-  if (sep && (rc = r->vpart.reserve(sizeof(double) * r->n_waves * r->max_chunk)) != VB_OK)
+  if (path == Path::ColumnPair &&
+      (rc = r->vpart.reserve(sizeof(double) * r->n_waves * r->max_chunk)) != VB_OK)
     return bail(rc);
   In di;
   if ((rc = di.stage(c, 0, init, P * n_problems)) != VB_OK) return bail(rc);
@@ -1270,66 +1282,237 @@ int vb_run_create(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const v
   return VB_OK;
 }
 
-// The per-step launches of full-rank / wide mean-field runs (one value_grad +
+// The per-step launches of full-rank / materialised mean-field runs (one value_grad +
 // update per step and problem), for steps [r->done, r->done + n_steps).
-static int advance_fr_steps(vb_ctx* c, vb_run* r, int64_t n_steps, const vb_noise* noise,
-                            bool host, const double* noise_base, size_t per_step, uint32_t k0,
-                            uint32_t k1) {
+static int advance_fr_steps(vb_ctx* c, vb_run* r, int64_t n_steps, const vbk::Noise& nz) {
   const size_t P = r->fi.P;
-    vbk::FrWork* W;
-    VB_TRY(fr_work(c, &W));
-    const uint32_t stride = noise->stream_stride ? noise->stream_stride : 1;
-    for (long long off = 0; off < n_steps; ++off) {
-      const long long step = r->done + off;
-      const double lr = r->sched.at(step);
-      for (long long q = 0; q < r->nprob; ++q) {
-        double* lam = r->lam.d() + q * P;
-        const double* eps =
-            host ? noise_base + ((size_t)q * n_steps + off) * per_step : nullptr;
-        double* hrow = step >= r->hist_start
-                           ? r->hist.d() + (q * r->n_hist + (step - r->hist_start)) * P
-                           : nullptr;
-        if (r->fr) {
-          // one problem with Philox draws: the adagrad step rides in the step's last
-          // kernel, which also prepares the next step of this advance (vb_fr.hip)
-          const bool fuse = r->nprob == 1 && !host && r->opt == VB_OPT_ADAGRAD && fr_fuse_enabled();
-          const vbk::MfUpdate up{r->ring.d() + q * P * r->W, r->W, step, lr, r->eps, hrow};
-          const vbk::FrNext nx{off + 1 < n_steps, (uint32_t)(noise->step + off + 1)};
-          VB_TRY(vbk::fr_value_grad(W, r->spec, lam, eps, k0, k1,
-                                    noise->stream + (uint32_t)q * stride,
-                                    (uint32_t)(noise->step + off),
-                                    r->values.d() + q * r->n_iters + step, r->grad.d(), c->stream,
-                                    r->nprob == 1 && step > 0, r, fuse ? &up : nullptr,
-                                    fuse ? &nx : nullptr));
-          if (fuse) continue;
-        }
-        if (!r->fr && r->opt == VB_OPT_ADAGRAD) {
-          // gradient pass applies the adagrad step and writes the history row
-          const vbk::MfUpdate up{r->ring.d() + q * P * r->W, r->W, step, lr, r->eps, hrow};
-          VB_TRY(vbk::mf_wide_value_grad(W, r->mspec, lam, eps, k0, k1,
-                                         noise->stream + (uint32_t)q * stride,
-                                         (uint32_t)(noise->step + off),
-                                         r->values.d() + q * r->n_iters + step, r->grad.d(),
-                                         c->stream, &up));
-          continue;
-        }
-        if (!r->fr)
-          VB_TRY(vbk::mf_wide_value_grad(W, r->mspec, lam, eps, k0, k1,
-                                         noise->stream + (uint32_t)q * stride,
-                                         (uint32_t)(noise->step + off),
-                                         r->values.d() + q * r->n_iters + step, r->grad.d(),
-                                         c->stream));
-        if (r->opt != VB_OPT_ADAGRAD) {
-          VB_HIP(vbk::launch_ia_update(r->opt, (long long)P, lam, r->grad.d(),
-                                       r->ring.d() + q * P * r->W, step, lr, r->eps, 0.0, hrow,
-                                       c->stream));
-        } else {
-          VB_HIP(vbk::launch_adagrad_update((long long)P, lam, r->grad.d(),
-                                            r->ring.d() + q * P * r->W, r->W, step, lr, r->eps,
-                                            nullptr, c->stream, hrow));
-        }
+  const bool fr = r->path == Path::FullRank;
+  const size_t per_step = (size_t)r->N * r->fi.D + (fr ? (size_t)r->N : 0);
+  vbk::FrWork* W;
+  VB_TRY(fr_work(c, &W));
+  for (long long off = 0; off < n_steps; ++off) {
+    const long long step = r->done + off;
+    const double lr = r->sched.at(step);
+    for (long long q = 0; q < r->nprob; ++q) {
+      double* lam = r->lam.d() + q * P;
+      vbk::Noise nq = nz.at(q, off);
+      if (nz.eps) nq.eps = nz.eps + ((size_t)q * n_steps + off) * per_step;
+      double* hrow = step >= r->hist_start
+                         ? r->hist.d() + (q * r->n_hist + (step - r->hist_start)) * P
+                         : nullptr;
+      double* value = r->values.d() + q * r->n_iters + step;
+      const vbk::MfUpdate up{r->ring.d() + q * P * r->W, r->W, step, lr, r->eps, hrow};
+      if (fr) {
+        // one problem with Philox draws: the adagrad step rides in the step's last
+        // kernel, which also prepares the next step of this advance (vb_fr.hip)
+        const bool fuse = r->nprob == 1 && !nz.eps && r->opt == VB_OPT_ADAGRAD && fr_fuse_enabled();
+        const vbk::FrNext nx{off + 1 < n_steps, (uint32_t)(nz.step + off + 1)};
+        VB_TRY(vbk::fr_value_grad(W, r->spec, lam, nq, value, r->grad.d(), c->stream,
+                                  r->nprob == 1 && step > 0, r, fuse ? &up : nullptr,
+                                  fuse ? &nx : nullptr));
+        if (fuse) continue;
+      } else {
+        // adagrad: the gradient pass applies the step and writes the history row
+        const bool fuse = r->opt == VB_OPT_ADAGRAD;
+        VB_TRY(vbk::mf_wide_value_grad(W, r->spec, lam, nq, value, r->grad.d(), c->stream,
+                                       fuse ? &up : nullptr));
+        if (fuse) continue;
+      }
+      if (r->opt != VB_OPT_ADAGRAD) {
+        VB_HIP(vbk::launch_ia_update(r->opt, (long long)P, lam, r->grad.d(), up.ring, step, lr,
+                                     r->eps, 0.0, hrow, c->stream));
+      } else {
+        VB_HIP(vbk::launch_adagrad_update((long long)P, lam, r->grad.d(), up.ring, r->W, step, lr,
+                                          r->eps, nullptr, c->stream, hrow));
       }
     }
+  }
+  return VB_OK;
+}
+
+// vb_run_advance on the full-rank / materialised paths
+static int advance_materialised(vb_ctx* c, vb_run* r, int64_t n_steps, const vbk::Noise& nz) {
+  const size_t P = r->fi.P;
+  const bool fr = r->path == Path::FullRank;
+  // one full-rank problem: a snapshot of lambda and the adagrad window lets the
+  // advance run again when a warm Newton-Schulz root launched too few
+  // iterations (they launch exactly the learnt count, no spares; vb_fr.hip
+  // fr_info)
+  // (and the workspace's warm state: the rerun's first step starts from the
+  // same previous root, power vectors and schedule as the failed pass did)
+  const bool snap = fr && r->nprob == 1;
+  const size_t snap_n = P + P * (size_t)r->W;
+  vbk::FrWork* W = nullptr;
+  if (fr) VB_TRY(fr_work(c, &W));
+  if (snap) {
+    VB_TRY(r->backup.reserve(snap_n * sizeof(double)));
+    VB_HIP(hipMemcpyAsync(r->backup.d(), r->lam.d(), P * sizeof(double), hipMemcpyDeviceToDevice,
+                          c->stream));
+    VB_HIP(hipMemcpyAsync(r->backup.d() + P, r->ring.d(), P * r->W * sizeof(double),
+                          hipMemcpyDeviceToDevice, c->stream));
+    if (int rc = vbk::fr_warm_save(W, c->stream)) return rc;
+  }
+  // lambda and the adagrad window back to the snapshot (before a rerun, and
+  // before returning an error: a failed advance leaves the run as it was)
+  auto restore = [&]() -> int {
+    VB_HIP(hipMemcpyAsync(r->lam.d(), r->backup.d(), P * sizeof(double),
+                          hipMemcpyDeviceToDevice, c->stream));
+    VB_HIP(hipMemcpyAsync(r->ring.d(), r->backup.d() + P, P * r->W * sizeof(double),
+                          hipMemcpyDeviceToDevice, c->stream));
+    return vbk::fr_warm_restore(W, c->stream);
+  };
+  // reruns of THIS advance: fr_info raises a count each time (Newton-Schulz by 3
+  // up to kFrNSMax, PCG x2 up to kFrPcgMax) and reports an error past those, so
+  // the loop ends by itself; the cap is a backstop.  r->fr_retries only counts
+  // (vb_run_fr_retries).
+  int reruns = 0;
+  for (bool rerun = false;; rerun = true) {
+    int rc = advance_fr_steps(c, r, n_steps, nz);
+    if (rc == VB_OK && fr) rc = sync(c);
+    bool again = false;
+    if (rc == VB_OK && fr) rc = vbk::fr_info(W, c->stream, snap ? &again : nullptr);
+    if (rc == VB_OK && again && ++reruns > 32)
+      rc = fail(VB_EDEVICE, "full-rank advance: too many reruns");
+    if (rc != VB_OK) {
+      if (snap) (void)restore();
+      return rc;
+    }
+    if (!again) {
+      if (rerun) vbk::fr_retry_done(W);
+      break;
+    }
+    ++r->fr_retries;
+    if (int rc2 = restore()) return rc2;
+  }
+  return VB_OK;
+}
+
+// vb_run_advance on the column-pair path: launches of at most max_chunk steps
+static int advance_column_pair(vb_ctx* c, vb_run* r, int64_t n_steps, const vbk::Noise& nz) {
+  const bool host = nz.eps != nullptr;
+  const size_t per_step = (size_t)r->N * r->fi.D;
+  long long off = 0;
+  while (off < n_steps) {
+    const int cs = (int)std::min<long long>(r->max_chunk, n_steps - off);
+    vbk::Noise nc = nz.at(0, off);
+    if (host) nc.eps = nz.eps + (size_t)off * per_step;
+    vbk::SepArgs a = sep_args(r->fi, r->N, r->obj, nc);
+    a.W = r->W;
+    a.n_steps = cs;
+    a.emit_grad = 0;
+    a.step0 = r->done + off;
+    a.hist_start = r->hist_start;
+    a.eps = r->eps;
+    a.lr = r->sched;
+    a.lam = r->lam.d();
+    a.ring = r->ring.d();
+    a.hist = r->hist.d();
+    a.vpart = r->vpart.d();
+    a.grad = nullptr;
+    std::pair<hipEvent_t, hipEvent_t>* ev;
+    HostTrace ht;
+    VB_TRY(r->next_event(cs, &ev));
+    ht.mark();
+    // timed runs: the pair bracketed by event records (hipExtLaunchKernel's own
+    // start / stop stamps instead measured ~0.2 us/step slower on the host path,
+    // interleaved, profiles/r05/headline_ab_c.log)
+    if (ev) VB_HIP(hipEventRecord(ev->first, c->stream));
+    VB_HIP(vbk::launch_sep(r->fi.kind, r->tgt, host, a, c->stream));
+    ht.mark();
+    VB_HIP(vbk::launch_sep_values(a.vpart, cs, a.n_waves, sep_c0(r->fi, a.pd != 0),
+                                  r->values.d() + a.step0, c->stream));
+    if (ev) VB_HIP(hipEventRecord(ev->second, c->stream));
+    ht.mark();
+    ht.print("sep advance: next_event | record + launch_sep | launch_values + record");
+    off += cs;
+  }
+  return VB_OK;
+}
+
+// vb_run_advance on the block-kernel path: one launch, or pre-drawn chunks
+static int advance_block(vb_ctx* c, vb_run* r, int64_t n_steps, const vbk::Noise& nz) {
+  const bool host = nz.eps != nullptr;
+  const int D = r->fi.D, N = r->N;
+  vbk::BlockArgs a = block_args(r->fi, N, r->obj, r->alpha, nz);
+  a.W = r->W;
+  a.n_steps = (int)n_steps;
+  a.emit_grad = 0;
+  a.opt = r->opt;
+  a.step0 = r->done;
+  a.hist_start = r->hist_start;
+  a.n_iters = r->n_iters;
+  a.n_hist = r->n_hist;
+  a.eps = r->eps;
+  a.lr = r->sched;
+  a.lam = r->lam.d();
+  a.ring = r->ring.d();
+  a.hist = r->hist.d();
+  a.values = r->values.d();
+  a.grad = nullptr;
+  a.noise_lq = nullptr;
+  if (!host && predraw_enabled(r->fi.kind, true, N, D, a.chivi || a.pd)) {
+    // Philox draws pre-drawn chunk by chunk by a throughput kernel over the
+    // whole chip, then consumed through the device-noise path: the same
+    // draws and log q partials, off the per-step critical path
+    const bool need_lq = a.chivi || a.pd;
+    const size_t per_step = (size_t)r->nprob * N * (D + (need_lq ? 1 : 0)) * sizeof(double);
+    const long long cap = std::max<long long>(1, (long long)(kPredrawBytes / per_step));
+    const int cmax = (int)std::min<long long>({n_steps, cap, (long long)kPredrawMaxSteps});
+    const size_t nb = (size_t)r->nprob * cmax * N * D * sizeof(double);
+    const size_t lb = (size_t)r->nprob * cmax * N * sizeof(double);
+    VB_TRY(r->noise.reserve(nb));
+    if (need_lq) VB_TRY(r->noise_lq.reserve(lb));
+    // more than one chunk: chunk k + 1 is drawn on the odd CUs while the block
+    // kernel runs chunk k on the even ones (two buffers, events between the
+    // streams; the same draws and bits as the serial order)
+    // (the streams are made on the first pre-drawn advance, whether or not it
+    // overlaps: creating them costs milliseconds, paid outside later timed runs)
+    const bool streams = predraw_overlap_enabled() && predraw_overlap_streams(c);
+    // (several problems only: one problem's pre-draw is a few us per chunk, and
+    // the cross-queue waits cost configs 1 / 2 ~3 %, profiles/r04/predraw_overlap_ab2.log)
+    const bool overlap = n_steps > cmax && streams && r->nprob >= kPredrawOverlapMinProblems;
+    if (overlap) {
+      VB_TRY(r->noise2.reserve(nb));
+      if (need_lq) VB_TRY(r->noise_lq2.reserve(lb));
+    }
+    hipStream_t pd_s = overlap ? c->pd_stream : c->stream;
+    hipStream_t blk_s = overlap ? c->blk_stream : c->stream;
+    hipEvent_t* ev = c->pd_ev;   // [0] start, [1..2] pre-draw of buffer b, [3..4] block of buffer b, [5] end
+    if (overlap) {
+      VB_HIP(hipEventRecord(ev[0], c->stream));
+      VB_HIP(hipStreamWaitEvent(pd_s, ev[0], 0));
+      VB_HIP(hipStreamWaitEvent(blk_s, ev[0], 0));
+    }
+    int k = 0;
+    for (long long off = 0; off < n_steps; off += cmax, ++k) {
+      const int cs = (int)std::min<long long>(cmax, n_steps - off);
+      const int bsel = overlap ? (k & 1) : 0;
+      double* nz_buf = bsel ? r->noise2.d() : r->noise.d();
+      double* nlq = need_lq ? (bsel ? r->noise_lq2.d() : r->noise_lq.d()) : nullptr;
+      if (overlap && k >= 2) VB_HIP(hipStreamWaitEvent(pd_s, ev[3 + bsel], 0));  // buffer consumed
+      VB_HIP(vbk::launch_block_predraw(r->fi, N, cs, (int)r->nprob, nz.at(0, off), nz_buf, nlq,
+                                       pd_s));
+      if (overlap) {
+        VB_HIP(hipEventRecord(ev[1 + bsel], pd_s));
+        VB_HIP(hipStreamWaitEvent(blk_s, ev[1 + bsel], 0));
+      }
+      vbk::BlockArgs b = a;
+      b.n_steps = cs;
+      b.step0 = r->done + off;
+      b.noise = nz_buf;
+      b.noise_lq = nlq;
+      VB_HIP(vbk::launch_block(r->fi.kind, r->tgt, true, b, (int)r->nprob, blk_s));
+      if (overlap) VB_HIP(hipEventRecord(ev[3 + bsel], blk_s));
+    }
+    if (overlap) {
+      // the caller's stream resumes after both streams' work (the pre-draw stream
+      // finished before the last block launch it fed)
+      VB_HIP(hipEventRecord(ev[5], blk_s));
+      VB_HIP(hipStreamWaitEvent(c->stream, ev[5], 0));
+    }
+  } else {
+    VB_HIP(vbk::launch_block(r->fi.kind, r->tgt, host, a, (int)r->nprob, c->stream));
+  }
   return VB_OK;
 }
 
@@ -1344,12 +1527,11 @@ int vb_run_advance(vb_run* r, int64_t n_steps, const vb_noise* noise) {
                 (long long)r->n_iters, (long long)r->done);
   if (n_steps == 0) return VB_OK;
   const bool host = noise->kind == VB_NOISE_HOST;
-  const int D = r->fi.D, N = r->N;
-  const size_t P = r->fi.P;
-  const size_t per_step = (size_t)N * D + (r->fr ? (size_t)N : 0);
+  const bool fr = r->path == Path::FullRank;
   if (host) {
     if (!noise->eps) return fail(VB_EINVAL, "host noise requires eps");
     if (ptr_class(noise->eps) < 0) return foreign_ptr_error(noise->eps);
+    const size_t per_step = (size_t)r->N * r->fi.D + (fr ? (size_t)r->N : 0);
     const size_t tot = per_step * n_steps * r->nprob;
     if (is_device_ptr(noise->eps)) {
       // used in place
@@ -1359,220 +1541,33 @@ int vb_run_advance(vb_run* r, int64_t n_steps, const vb_noise* noise) {
                             c->stream));
     }
   }
-  const double* noise_base =
-      host ? (is_device_ptr(noise->eps) ? noise->eps : r->noise.d()) : nullptr;
-  uint32_t k0, k1;
-  key_of(noise->seed, &k0, &k1);
+  const vbk::Noise nz = noise_of(
+      noise, host ? (is_device_ptr(noise->eps) ? noise->eps : r->noise.d()) : nullptr);
 
+  // (the column-pair path times each of its launches instead)
   std::pair<hipEvent_t, hipEvent_t>* call_ev = nullptr;
-  if (!r->sep) {
+  if (r->path != Path::ColumnPair) {
     VB_TRY(r->next_event(n_steps, &call_ev));
     if (call_ev) VB_HIP(hipEventRecord(call_ev->first, c->stream));
   }
-  if (r->fr || r->wide) {
-    // one full-rank problem: a snapshot of lambda and the adagrad window lets the
-    // advance run again when a warm Newton-Schulz root launched too few
-    // iterations (they launch exactly the learnt count, no spares; vb_fr.hip
-    // fr_info)
-    // (and the workspace's warm state: the rerun's first step starts from the
-    // same previous root, power vectors and schedule as the failed pass did)
-    const bool snap = r->fr && r->nprob == 1;
-    const size_t snap_n = P + P * (size_t)r->W;
-    vbk::FrWork* W = nullptr;
-    if (r->fr) VB_TRY(fr_work(c, &W));
-    if (snap) {
-      VB_TRY(r->backup.reserve(snap_n * sizeof(double)));
-      VB_HIP(hipMemcpyAsync(r->backup.d(), r->lam.d(), P * sizeof(double), hipMemcpyDeviceToDevice,
-                            c->stream));
-      VB_HIP(hipMemcpyAsync(r->backup.d() + P, r->ring.d(), P * r->W * sizeof(double),
-                            hipMemcpyDeviceToDevice, c->stream));
-      if (int rc = vbk::fr_warm_save(W, c->stream)) return rc;
-    }
-    // lambda and the adagrad window back to the snapshot (before a rerun, and
-    // before returning an error: a failed advance leaves the run as it was)
-    auto restore = [&]() -> int {
-      VB_HIP(hipMemcpyAsync(r->lam.d(), r->backup.d(), P * sizeof(double),
-                            hipMemcpyDeviceToDevice, c->stream));
-      VB_HIP(hipMemcpyAsync(r->ring.d(), r->backup.d() + P, P * r->W * sizeof(double),
-                            hipMemcpyDeviceToDevice, c->stream));
-      return vbk::fr_warm_restore(W, c->stream);
-    };
-    // reruns of THIS advance: fr_info raises a count each time (Newton-Schulz by 3
-    // up to kFrNSMax, PCG x2 up to kFrPcgMax) and reports an error past those, so
-    // the loop ends by itself; the cap is a backstop.  r->fr_retries only counts
-    // (vb_run_fr_retries).
-    int reruns = 0;
-    for (bool rerun = false;; rerun = true) {
-      int rc = advance_fr_steps(c, r, n_steps, noise, host, noise_base, per_step, k0, k1);
-      if (rc == VB_OK && r->fr) rc = sync(c);
-      bool again = false;
-      if (rc == VB_OK && r->fr) rc = vbk::fr_info(W, c->stream, snap ? &again : nullptr);
-      if (rc == VB_OK && again && ++reruns > 32)
-        rc = fail(VB_EDEVICE, "full-rank advance: too many reruns");
-      if (rc != VB_OK) {
-        if (snap) (void)restore();
-        return rc;
-      }
-      if (!again) {
-        if (rerun) vbk::fr_retry_done(W);
-        break;
-      }
-      ++r->fr_retries;
-      if (int rc2 = restore()) return rc2;
-    }
-  } else if (r->sep) {
-    ht0.mark();
-    ht0.print("advance entry -> sep branch");
-    long long off = 0;
-    while (off < n_steps) {
-      const int cs = (int)std::min<long long>(r->max_chunk, n_steps - off);
-      vbk::SepArgs a{};
-      a.D = D;
-      a.N = N;
-      a.W = r->W;
-      a.n_pairs = r->n_waves;
-      a.n_steps = cs;
-      a.emit_grad = 0;
-      a.pd = r->obj == VB_OBJ_KLVI_PD ? (r->fi.kind == VB_FAMILY_MF_T ? 2 : 1) : 0;
-      a.step0 = r->done + off;
-      a.hist_start = r->hist_start;
-      a.rng_step0 = (long long)noise->step + off;
-      a.n_waves = r->n_waves;
-      a.t_scale = r->fi.t_scale;
-      a.shape = r->fi.shape;
-      a.eps = r->eps;
-      a.lr = r->sched;
-      a.lam = r->lam.d();
-      a.ring = r->ring.d();
-      a.hist = r->hist.d();
-      a.vpart = r->vpart.d();
-      a.grad = nullptr;
-      a.noise = host ? noise_base + (size_t)off * per_step : nullptr;
-      a.k0 = k0;
-      a.k1 = k1;
-      a.stream = noise->stream;
-      std::pair<hipEvent_t, hipEvent_t>* ev;
-      HostTrace ht;
-      VB_TRY(r->next_event(cs, &ev));
-      ht.mark();
-      // timed runs: the pair bracketed by event records (hipExtLaunchKernel's own
-      // start / stop stamps instead measured ~0.2 us/step slower on the host path,
-      // interleaved, profiles/r05/headline_ab_c.log)
-      if (ev) VB_HIP(hipEventRecord(ev->first, c->stream));
-      VB_HIP(vbk::launch_sep(r->fi.kind, r->tgt, host, a, c->stream));
-      ht.mark();
-      VB_HIP(vbk::launch_sep_values(a.vpart, cs, a.n_waves, sep_c0(r->fi, a.pd != 0),
-                                    r->values.d() + a.step0, c->stream));
-      if (ev) VB_HIP(hipEventRecord(ev->second, c->stream));
-      ht.mark();
-      ht.print("sep advance: next_event | record + launch_sep | launch_values + record");
-      off += cs;
-    }
-  } else {
-    vbk::BlockArgs a{};
-    a.pf = block_pf_enabled();
-    a.D = D;
-    a.N = N;
-    a.W = r->W;
-    a.P = (int)P;
-    a.n_steps = (int)n_steps;
-    a.emit_grad = 0;
-    a.chivi = r->obj == VB_OBJ_CHIVI;
-    a.pd = r->obj == VB_OBJ_KLVI_PD;
-    a.opt = r->opt;
-    a.step0 = r->done;
-    a.hist_start = r->hist_start;
-    a.n_iters = r->n_iters;
-    a.n_hist = r->n_hist;
-    a.rng_step0 = (long long)noise->step;
-    a.alpha = r->alpha;
-    a.t_scale = r->fi.t_scale;
-    a.shape = r->fi.shape;
-    a.t_const = r->fi.t_const;
-    a.df = r->fi.df;
-    a.eps = r->eps;
-    a.lr = r->sched;
-    a.lam = r->lam.d();
-    a.ring = r->ring.d();
-    a.hist = r->hist.d();
-    a.values = r->values.d();
-    a.grad = nullptr;
-    a.noise = noise_base;
-    a.noise_lq = nullptr;
-    a.k0 = k0;
-    a.k1 = k1;
-    a.stream = noise->stream;
-    a.stream_stride = noise->stream_stride ? noise->stream_stride : 1;
-    if (!host && predraw_enabled(r->fi.kind, true, N, D, a.chivi || a.pd)) {
-      // Philox draws pre-drawn chunk by chunk by a throughput kernel over the
-      // whole chip, then consumed through the device-noise path: the same
-      // draws and log q partials, off the per-step critical path
-      const bool need_lq = a.chivi || a.pd;
-      const size_t per_step = (size_t)r->nprob * N * (D + (need_lq ? 1 : 0)) * sizeof(double);
-      const long long cap = std::max<long long>(1, (long long)(kPredrawBytes / per_step));
-      const int cmax = (int)std::min<long long>({n_steps, cap, (long long)kPredrawMaxSteps});
-      const size_t nb = (size_t)r->nprob * cmax * N * D * sizeof(double);
-      const size_t lb = (size_t)r->nprob * cmax * N * sizeof(double);
-      VB_TRY(r->noise.reserve(nb));
-      if (need_lq) VB_TRY(r->noise_lq.reserve(lb));
-      // more than one chunk: chunk k + 1 is drawn on the odd CUs while the block
-      // kernel runs chunk k on the even ones (two buffers, events between the
-      // streams; the same draws and bits as the serial order)
-      // (the streams are made on the first pre-drawn advance, whether or not it
-      // overlaps: creating them costs milliseconds, paid outside later timed runs)
-      const bool streams = predraw_overlap_enabled() && predraw_overlap_streams(c);
-      // (several problems only: one problem's pre-draw is a few us per chunk, and
-      // the cross-queue waits cost configs 1 / 2 ~3 %, profiles/r04/predraw_overlap_ab2.log)
-      const bool overlap = n_steps > cmax && streams && r->nprob >= kPredrawOverlapMinProblems;
-      if (overlap) {
-        VB_TRY(r->noise2.reserve(nb));
-        if (need_lq) VB_TRY(r->noise_lq2.reserve(lb));
-      }
-      hipStream_t pd_s = overlap ? c->pd_stream : c->stream;
-      hipStream_t blk_s = overlap ? c->blk_stream : c->stream;
-      hipEvent_t* ev = c->pd_ev;   // [0] start, [1..2] pre-draw of buffer b, [3..4] block of buffer b, [5] end
-      if (overlap) {
-        VB_HIP(hipEventRecord(ev[0], c->stream));
-        VB_HIP(hipStreamWaitEvent(pd_s, ev[0], 0));
-        VB_HIP(hipStreamWaitEvent(blk_s, ev[0], 0));
-      }
-      int k = 0;
-      for (long long off = 0; off < n_steps; off += cmax, ++k) {
-        const int cs = (int)std::min<long long>(cmax, n_steps - off);
-        const int bsel = overlap ? (k & 1) : 0;
-        double* nz = bsel ? r->noise2.d() : r->noise.d();
-        double* nlq = need_lq ? (bsel ? r->noise_lq2.d() : r->noise_lq.d()) : nullptr;
-        if (overlap && k >= 2) VB_HIP(hipStreamWaitEvent(pd_s, ev[3 + bsel], 0));  // buffer consumed
-        VB_HIP(vbk::launch_block_predraw(r->fi.kind, D, N, cs, (int)r->nprob, k0, k1, a.stream,
-                                         a.stream_stride, (long long)noise->step + off,
-                                         r->fi.t_scale, r->fi.shape, r->fi.df, r->fi.t_const,
-                                         nz, nlq, pd_s));
-        if (overlap) {
-          VB_HIP(hipEventRecord(ev[1 + bsel], pd_s));
-          VB_HIP(hipStreamWaitEvent(blk_s, ev[1 + bsel], 0));
-        }
-        vbk::BlockArgs b = a;
-        b.n_steps = cs;
-        b.step0 = r->done + off;
-        b.noise = nz;
-        b.noise_lq = nlq;
-        VB_HIP(vbk::launch_block(r->fi.kind, r->tgt, true, b, (int)r->nprob, blk_s));
-        if (overlap) VB_HIP(hipEventRecord(ev[3 + bsel], blk_s));
-      }
-      if (overlap) {
-        // the caller's stream resumes after both streams' work (the pre-draw stream
-        // finished before the last block launch it fed)
-        VB_HIP(hipEventRecord(ev[5], blk_s));
-        VB_HIP(hipStreamWaitEvent(c->stream, ev[5], 0));
-      }
-    } else {
-      VB_HIP(vbk::launch_block(r->fi.kind, r->tgt, host, a, (int)r->nprob, c->stream));
-    }
+  switch (r->path) {
+    case Path::FullRank:
+    case Path::Materialised:
+      VB_TRY(advance_materialised(c, r, n_steps, nz));
+      break;
+    case Path::ColumnPair:
+      ht0.mark();
+      ht0.print("advance entry -> sep branch");
+      VB_TRY(advance_column_pair(c, r, n_steps, nz));
+      break;
+    case Path::Block:
+      VB_TRY(advance_block(c, r, n_steps, nz));
+      break;
   }
   if (call_ev) VB_HIP(hipEventRecord(call_ev->second, c->stream));
   r->done += n_steps;
-  if (r->wide) return sync(c);
-  if (r->fr) {
+  if (r->path == Path::Materialised) return sync(c);
+  if (fr) {
     VB_TRY(sync(c));
     vbk::FrWork* W;
     VB_TRY(fr_work(c, &W));
@@ -1806,7 +1801,9 @@ int vb_log_weights_rows(vb_ctx* c, const vb_family* fam, const vb_target* tgt,
   if (rows > 65535) return fail(VB_EINVAL, "rows must be <= 65535");
   if (fi.kind == VB_FAMILY_FR_T) return fail(VB_EUNSUPPORTED, "rows of log weights: mean-field families only");
   if (noise->kind != VB_NOISE_PHILOX) return fail(VB_EINVAL, "rows of log weights need Philox noise");
-  if ((!vbk::target_separable(tgt->kind) && fi.D > vbk::kBlockDMax) || materialised_target(tgt->kind))
+  // (a pairing choose_path rejects has no rows kernel either)
+  Path path;
+  if (choose_path({fi.kind, tgt->kind, fi.D}, &path) != VB_OK || path == Path::Materialised)
     return fail(VB_EUNSUPPORTED, "rows of log weights: D <= %d or a separable device target",
                 vbk::kBlockDMax);
   if (m == 0 || rows == 0) return VB_OK;
@@ -1814,12 +1811,9 @@ int vb_log_weights_rows(vb_ctx* c, const vb_family* fam, const vb_target* tgt,
   Out dlw;
   VB_TRY(dl.stage(c, 0, lam, 2 * (size_t)fi.D * rows));
   VB_TRY(dlw.stage(c, 2, lw_out, (size_t)m * rows));
-  uint32_t k0, k1;
-  key_of(noise->seed, &k0, &k1);
-  VB_HIP(vbk::launch_log_weights(fi.kind, tgt->kind, fi.D, m, dl.d, fi.t_scale, fi.shape, fi.df,
-                                 fi.t_const, nullptr, k0, k1, noise->stream,
-                                 (uint32_t)noise->step, dlw.d, nullptr, c->stream, (int)rows,
-                                 noise->stream_stride));
+  vbk::Noise nz = noise_of(noise, nullptr);
+  nz.stride = noise->stream_stride;  // as given: 0 keeps every row on one stream
+  VB_HIP(vbk::launch_log_weights(fi, tgt->kind, m, dl.d, nz, dlw.d, nullptr, c->stream, (int)rows));
   VB_TRY(dlw.finish(c));
   return sync(c);
 }
@@ -1832,77 +1826,36 @@ int vb_log_weights(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const 
   vbk::GlmHead glm{};
   VB_TRY(check_target(tgt, fi.D, &glm));
   if (!lam || !noise || !lw_out || m < 0) return fail(VB_EINVAL, "null argument");
-  VB_TRY(require_fr(fi.kind, tgt->kind));
-  if (fi.kind == VB_FAMILY_FR_T) {
-    const bool host = noise->kind == VB_NOISE_HOST;
-    if (host && !noise->eps) return fail(VB_EINVAL, "host noise requires eps");
-    if (m == 0) return VB_OK;
-    In dl, dn;
-    Out dlw, dxs;
-    VB_TRY(dl.stage(c, 0, lam, fi.P));
-    if (host) VB_TRY(dn.stage(c, 1, noise->eps, (size_t)m * fi.D + m));
-    VB_TRY(dlw.stage(c, 2, lw_out, (size_t)m));
-    VB_TRY(dxs.stage(c, 3, samples_out, samples_out ? (size_t)m * fi.D : 0));
-    const double* tp;
-    double tc;
-    VB_TRY(target_params(c, tgt->kind == VB_TARGET_REGRESSION ? 8 : 4, tgt, &tp, &tc));
-    vbk::FrSpec f{};
-    f.glm = glm;
-    f.host = host_of(tgt);
-    f.D = fi.D;
-    f.tgt = tgt->kind;
-    f.df = fi.df;
-    f.t_const = fi.t_const;
-    f.tparams = tp;
-    f.tconst = tc;
-    uint32_t k0, k1;
-    key_of(noise->seed, &k0, &k1);
-    vbk::FrWork* W;
-    VB_TRY(fr_work(c, &W));
-    VB_TRY(vbk::fr_log_weights(W, f, dl.d, m, host ? dn.d : nullptr, k0, k1, noise->stream,
-                               (uint32_t)noise->step, dlw.d, dxs.d, c->stream));
-    VB_TRY(dlw.finish(c));
-    VB_TRY(dxs.finish(c));
-    return sync(c);
-  }
-  if ((!vbk::target_separable(tgt->kind) && fi.D > vbk::kBlockDMax) ||
-      materialised_target(tgt->kind)) {
-    const bool host = noise->kind == VB_NOISE_HOST;
-    if (host && !noise->eps) return fail(VB_EINVAL, "host noise requires eps");
-    if (m == 0) return VB_OK;
-    In dl, dn;
-    Out dlw, dxs;
-    VB_TRY(dl.stage(c, 0, lam, fi.P));
-    if (host) VB_TRY(dn.stage(c, 1, noise->eps, (size_t)m * fi.D));
-    VB_TRY(dlw.stage(c, 2, lw_out, (size_t)m));
-    VB_TRY(dxs.stage(c, 3, samples_out, samples_out ? (size_t)m * fi.D : 0));
-    uint32_t k0, k1;
-    key_of(noise->seed, &k0, &k1);
-    vbk::FrWork* W;
-    VB_TRY(fr_work(c, &W));
-    const double* tp;
-    double tc;
-    VB_TRY(target_params(c, 8, tgt, &tp, &tc));
-    VB_TRY(vbk::mf_wide_log_weights(W, mf_spec(fi, tgt, nullptr, tp, glm), dl.d, m, host ? dn.d : nullptr,
-                                    k0, k1, noise->stream, (uint32_t)noise->step, dlw.d, dxs.d,
-                                    c->stream));
-    VB_TRY(dlw.finish(c));
-    VB_TRY(dxs.finish(c));
-    return sync(c);
-  }
+  Path path;
+  VB_TRY(choose_path({fi.kind, tgt->kind, fi.D}, &path));
+  const bool fr = path == Path::FullRank;
   const bool host = noise->kind == VB_NOISE_HOST;
   if (host && !noise->eps) return fail(VB_EINVAL, "host noise requires eps");
+  // (the fused kernels' launch function takes m == 0 itself)
+  if (m == 0 && (fr || path == Path::Materialised)) return VB_OK;
   In dl, dn;
   Out dlw, dxs;
-  VB_TRY(dl.stage(c, 0, lam, 2 * (size_t)fi.D));
-  if (host) VB_TRY(dn.stage(c, 1, noise->eps, (size_t)m * fi.D));
+  VB_TRY(dl.stage(c, 0, lam, fi.P));
+  // full rank: each draw carries its scale s beside z
+  if (host) VB_TRY(dn.stage(c, 1, noise->eps, (size_t)m * fi.D + (fr ? m : 0)));
   VB_TRY(dlw.stage(c, 2, lw_out, (size_t)m));
   VB_TRY(dxs.stage(c, 3, samples_out, samples_out ? (size_t)m * fi.D : 0));
-  uint32_t k0, k1;
-  key_of(noise->seed, &k0, &k1);
-  VB_HIP(vbk::launch_log_weights(fi.kind, tgt->kind, fi.D, m, dl.d, fi.t_scale, fi.shape, fi.df,
-                                 fi.t_const, host ? dn.d : nullptr, k0, k1, noise->stream,
-                                 (uint32_t)noise->step, dlw.d, dxs.d, c->stream));
+  const vbk::Noise nz = noise_of(noise, host ? dn.d : nullptr);
+  if (path == Path::ColumnPair || path == Path::Block) {
+    VB_HIP(vbk::launch_log_weights(fi, tgt->kind, m, dl.d, nz, dlw.d, dxs.d, c->stream));
+  } else {
+    const double* tp;
+    double tc;
+    const int slot = (!fr || tgt->kind == VB_TARGET_REGRESSION) ? kSlotGlm : kSlotTparamsLw;
+    VB_TRY(target_params(c, slot, tgt, &tp, &tc));
+    vbk::FrWork* W;
+    VB_TRY(fr_work(c, &W));
+    const vbk::Spec f = make_spec(fi, tgt, nullptr, tp, tc, glm);
+    if (fr)
+      VB_TRY(vbk::fr_log_weights(W, f, dl.d, m, nz, dlw.d, dxs.d, c->stream));
+    else
+      VB_TRY(vbk::mf_wide_log_weights(W, f, dl.d, m, nz, dlw.d, dxs.d, c->stream));
+  }
   VB_TRY(dlw.finish(c));
   VB_TRY(dxs.finish(c));
   return sync(c);

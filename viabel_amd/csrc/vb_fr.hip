@@ -1902,21 +1902,21 @@ int fr_pcg(FrWork* W, int D, hipStream_t st, int N = 0, const double* rw = nullp
   return 0;
 }
 
-// s (n) and z (n x D) into the workspace; host_eps = [s (n), z (n x D)] on the device
-int fr_draw(FrWork* W, int D, long long n, double df, const double* host_eps, uint32_t k0,
-            uint32_t k1, uint32_t stream, uint32_t step, const double** s_out,
+// s (n) and z (n x D) into the workspace; nz.eps = [s (n), z (n x D)] on the device
+int fr_draw(FrWork* W, const Family& f, long long n, const Noise& nz, const double** s_out,
             const double** z_out, hipStream_t st) {
   W->prep_owner = nullptr;
-  if (host_eps) {
-    *s_out = host_eps;
-    *z_out = host_eps + n;
+  if (nz.eps) {
+    *s_out = nz.eps;
+    *z_out = nz.eps + n;
     return 0;
   }
+  const int D = f.D;
   if (int rc = reserve_n(W, D, n)) return rc;
-  Rng rng{k0, k1, stream};
+  Rng rng{nz.k0, nz.k1, nz.stream};
   const long long tot = n * ((D + 1) / 2 + 1);
-  hipLaunchKernelGGL(fr_noise_kernel, dim3(blocks(tot)), dim3(256), 0, st, D, n, rng, step, df,
-                     W->Z.d(), W->s.d());
+  hipLaunchKernelGGL(fr_noise_kernel, dim3(blocks(tot)), dim3(256), 0, st, D, n, rng,
+                     (uint32_t)nz.step, f.df, W->Z.d(), W->s.d());
   FR_HIP(hipGetLastError());
   *s_out = W->s.d();
   *z_out = W->Z.d();
@@ -1955,11 +1955,12 @@ int fr_target(FrWork* W, int tgt, int D, long long n, const double* tparams, dou
 
 // One KLVI / CHIVI value + gradient (vb.py:236-266) at lam, gradient into grad[P]
 // and the value into *value (device pointers).
-int fr_value_grad(FrWork* W, const FrSpec& f, const double* lam, const double* host_eps,
-                  uint32_t k0, uint32_t k1, uint32_t stream, uint32_t step, double* value,
+int fr_value_grad(FrWork* W, const Spec& f, const double* lam, const Noise& nz, double* value,
                   double* grad, hipStream_t st, bool warm, const void* owner,
                   const MfUpdate* up, const FrNext* next) {
-  const int D = f.D, N = f.N;
+  const int D = f.fam.D, N = f.N;
+  const double* host_eps = nz.eps;
+  const uint32_t k0 = nz.k0, k1 = nz.k1, stream = nz.stream, step = (uint32_t)nz.step;
   // fused step: adagrad in the last kernel, Philox draws reduced with zz by their
   // own kernel, logp (corr_gauss) from the target GEMM's row partials, the mean
   // gradient in pcg_init's extra blocks; `ready`: the previous fused step of this
@@ -1977,10 +1978,10 @@ int fr_value_grad(FrWork* W, const FrSpec& f, const double* lam, const double* h
     z = W->Z.d();
   } else if (fused) {
     hipLaunchKernelGGL(fr_noise_rows_kernel, dim3(N), dim3(256), 0, st, D, Rng{k0, k1, stream},
-                       step, f.df, W->Z.d(), W->s.d(), W->zz.d());
+                       step, f.fam.df, W->Z.d(), W->s.d(), W->zz.d());
     s = W->s.d();
     z = W->Z.d();
-  } else if (int rc = fr_draw(W, D, N, f.df, host_eps, k0, k1, stream, step, &s, &z, st)) {
+  } else if (int rc = fr_draw(W, f.fam, N, nz, &s, &z, st)) {
     return rc;
   }
   if (int rc = fr_transform(W, D, N, lam, s, z, W->X.d(), st)) return rc;
@@ -2008,13 +2009,13 @@ int fr_value_grad(FrWork* W, const FrSpec& f, const double* lam, const double* h
   // cotangent of S: G_S = Z^T diag(r / s) G, r the objective's weights
   GemmOp g = mm(D, D, N, z, true, W->G.d(), false, W->GS.d());
   if (weights_fused() && N <= 512 && gemm_detail::glds_ok_shape(g)) {
-    WeightsArgs wa{N, D, f.chivi, f.pd, f.alpha, f.df, f.t_const, W->logp.d(), W->zz.d(), s,
+    WeightsArgs wa{N, D, f.chivi, f.pd, f.alpha, f.fam.df, f.fam.t_const, W->logp.d(), W->zz.d(), s,
                    W->scal.d(), W->r.d(), W->rk.d(), value,
                    lp_parts ? W->lp_part.d() : nullptr, lp_parts ? nlp : 0, f.tconst};
     FR_HIP(gemm_hook<WeightsHook>(g, wa, st));
   } else {
     hipLaunchKernelGGL(fr_weights_kernel, dim3(1), dim3(1024), 0, st, N, D, f.chivi, f.pd, f.alpha,
-                       f.df, f.t_const, W->logp.d(), W->zz.d(), s, W->scal.d(), W->r.d(),
+                       f.fam.df, f.fam.t_const, W->logp.d(), W->zz.d(), s, W->scal.d(), W->r.d(),
                        W->rk.d(), value, lp_parts ? W->lp_part.d() : nullptr, lp_parts ? nlp : 0,
                        f.tconst);
     g.kscale = W->rk.d();
@@ -2064,7 +2065,7 @@ int fr_value_grad(FrWork* W, const FrSpec& f, const double* lam, const double* h
   a.hrow = up->hrow;
   a.rng = Rng{k0, k1, stream};
   a.next_step = prep ? next->step : 0;
-  a.df = f.df;
+  a.df = f.fam.df;
   a.z = W->Z.d();
   a.s = W->s.d();
   a.zz = W->zz.d();
@@ -2087,30 +2088,30 @@ int fr_value_grad(FrWork* W, const FrSpec& f, const double* lam, const double* h
 }
 
 // log q(x) for arbitrary x (n x D) at lam
-int fr_logdensity(FrWork* W, int D, double df, double t_const, const double* lam, const double* x,
-                  long long n, double* out, hipStream_t st) {
+int fr_logdensity(FrWork* W, const Family& f, const double* lam, const double* x, long long n,
+                  double* out, hipStream_t st) {
+  const int D = f.D;
   if (int rc = fr_prepare(W, D, lam, st)) return rc;
   if (int rc = reserve_n(W, D, n)) return rc;
   hipLaunchKernelGGL(fr_center_kernel, dim3(blocks(n * D)), dim3(256), 0, st, D, n, x, lam,
                      W->X.d());
   FR_HIP(gemm(mm((int)n, D, D, W->X.d(), false, W->E.d(), true, W->G.d()), st));
   hipLaunchKernelGGL(fr_logq_kernel, dim3(blocks(n, 4)), dim3(256), 0, st, D, n, W->G.d(), W->w.d(),
-                     W->scal.d(), df, t_const, out);
+                     W->scal.d(), f.df, f.t_const, out);
   FR_HIP(hipGetLastError());
   return 0;
 }
 
 // log weights lw = log p(x) - log q(x), x ~ q (experiments.py:60-63).  log q uses
 // the Mahalanobis invariant z^T z / s^2.
-int fr_log_weights(FrWork* W, const FrSpec& f, const double* lam, long long m,
-                   const double* host_eps, uint32_t k0, uint32_t k1, uint32_t stream,
-                   uint32_t step, double* lw, double* xs, hipStream_t st) {
+int fr_log_weights(FrWork* W, const Spec& f, const double* lam, long long m, const Noise& nz,
+                   double* lw, double* xs, hipStream_t st) {
   W->prep_owner = nullptr;
-  const int D = f.D;
+  const int D = f.fam.D;
   if (int rc = fr_sqrt(W, D, lam, st, false)) return rc;
   if (int rc = reserve_n(W, D, m)) return rc;
   const double *s, *z;
-  if (int rc = fr_draw(W, D, m, f.df, host_eps, k0, k1, stream, step, &s, &z, st)) return rc;
+  if (int rc = fr_draw(W, f.fam, m, nz, &s, &z, st)) return rc;
   double* x = xs ? xs : W->X.d();
   if (int rc = fr_transform(W, D, m, lam, s, z, x, st)) return rc;
   if (f.tgt == kTargetCorrGauss) {
@@ -2123,7 +2124,7 @@ int fr_log_weights(FrWork* W, const FrSpec& f, const double* lam, long long m,
                        nullptr, 0.0, 0, W->zz.d(), nullptr);
   }
   // chivi weights with alpha = 1 would rescale; compute lw directly instead
-  FR_HIP(launch_fr_lw(D, m, f.df, f.t_const, W->logp.d(), W->zz.d(), s, W->scal.d(), lw, st));
+  FR_HIP(launch_fr_lw(f.fam, m, W->logp.d(), W->zz.d(), s, W->scal.d(), lw, st));
   return 0;
 }
 
@@ -2140,11 +2141,10 @@ __global__ __launch_bounds__(256) void fr_lw_kernel(int D, long long m, double d
 }
 }  // namespace
 
-hipError_t launch_fr_lw(int D, long long m, double df, double t_const, const double* logp,
-                        const double* zz, const double* s, const double* scal, double* lw,
-                        hipStream_t st) {
-  hipLaunchKernelGGL(fr_lw_kernel, dim3(blocks(m)), dim3(256), 0, st, D, m, df, t_const, logp, zz,
-                     s, scal, lw);
+hipError_t launch_fr_lw(const Family& f, long long m, const double* logp, const double* zz,
+                        const double* s, const double* scal, double* lw, hipStream_t st) {
+  hipLaunchKernelGGL(fr_lw_kernel, dim3(blocks(m)), dim3(256), 0, st, f.D, m, f.df, f.t_const, logp,
+                     zz, s, scal, lw);
   return hipGetLastError();
 }
 
@@ -2367,11 +2367,10 @@ __global__ __launch_bounds__(64 * kGradWaves) void mfw_grad_kernel(MfwGradArgs A
 
 }  // namespace
 
-int mf_wide_value_grad(FrWork* W, const MfSpec& f, const double* lam, const double* host_eps,
-                       uint32_t k0, uint32_t k1, uint32_t stream, uint32_t step, double* value,
-                       double* grad, hipStream_t st, const MfUpdate* up) {
+int mf_wide_value_grad(FrWork* W, const Spec& f, const double* lam, const Noise& nz,
+                       double* value, double* grad, hipStream_t st, const MfUpdate* up) {
   W->prep_owner = nullptr;
-  const int D = f.D, N = f.N;
+  const int D = f.fam.D, N = f.N;
   if (int rc = reserve_d(W, 1, st)) return rc;
   if (int rc = reserve_n(W, D, N)) return rc;
   if (f.tgt == kTargetCorrGauss)
@@ -2384,18 +2383,16 @@ int mf_wide_value_grad(FrWork* W, const MfSpec& f, const double* lam, const doub
     nparts = mfw_rows_parts(D);
     lp = W->Z.d();
     lq = lp + (size_t)nparts * N;
-    FR_HIP(launch_mfw_rows(f.fam, f.tgt, D, N, lam, f.t_scale, f.shape, f.df, f.t_const,
-                           f.chivi || f.pd, host_eps, k0, k1, stream, step, W->X.d(), W->G.d(),
-                           lp, lq, st));
+    FR_HIP(launch_mfw_rows(f.fam, f.tgt, N, lam, f.chivi || f.pd, nz, W->X.d(), W->G.d(), lp, lq,
+                           st));
   } else {
-    FR_HIP(launch_sample(f.fam, D, N, lam, f.t_scale, f.shape, host_eps, k0, k1, stream, step,
-                         W->X.d(), st));
+    FR_HIP(launch_sample(f.fam, N, lam, nz, W->X.d(), st));
     if (int rc = eval_target(W, f.tgt, f.host, f.tparams, f.glm, D, N, W->X.d(), W->logp.d(), W->G.d(), st))
       return rc;
     if (f.chivi || f.pd)
-      FR_HIP(launch_family_logdensity(f.fam, D, N, lam, f.df, f.t_const, W->X.d(), W->zz.d(), st));
+      FR_HIP(launch_family_logdensity(f.fam, N, lam, W->X.d(), W->zz.d(), st));
   }
-  const double c0 = f.fam == 1 ? 0.0 : 0.5 * D * (1.0 + kLog2Pi);
+  const double c0 = f.fam.kind == 1 ? 0.0 : 0.5 * D * (1.0 + kLog2Pi);
   const bool wfuse = f.chivi && N <= 1024;
   if (!wfuse)
     hipLaunchKernelGGL(mfw_weights_kernel, dim3(1), dim3(1024), 0, st, N, D, f.chivi, f.pd,
@@ -2444,23 +2441,21 @@ __global__ __launch_bounds__(256) void sub_kernel(long long n, const double* a, 
 }  // namespace
 
 // lw = log p(x) - log q(x), x ~ q, for any mean-field family / target / D
-int mf_wide_log_weights(FrWork* W, const MfSpec& f, const double* lam, long long m,
-                        const double* host_eps, uint32_t k0, uint32_t k1, uint32_t stream,
-                        uint32_t step, double* lw, double* xs, hipStream_t st) {
+int mf_wide_log_weights(FrWork* W, const Spec& f, const double* lam, long long m, const Noise& nz,
+                        double* lw, double* xs, hipStream_t st) {
   W->prep_owner = nullptr;
-  const int D = f.D;
+  const int D = f.fam.D;
   if (int rc = reserve_d(W, 1, st)) return rc;
   if (int rc = reserve_n(W, D, m)) return rc;
   double* x = xs ? xs : W->X.d();
-  if (f.fam == 1 && !host_eps) {
+  if (f.fam.kind == 1 && !nz.eps) {
     // the t family's Philox log-weight draws are Bailey pairs (as logw_row_kernel)
-    FR_HIP(launch_sample_bailey(D, m, lam, f.df, k0, k1, stream, step, x, st));
+    FR_HIP(launch_sample_bailey(f.fam, m, lam, nz, x, st));
   } else {
-    FR_HIP(launch_sample(f.fam, D, m, lam, f.t_scale, f.shape, host_eps, k0, k1, stream, step, x,
-                         st));
+    FR_HIP(launch_sample(f.fam, m, lam, nz, x, st));
   }
   if (int rc = eval_target(W, f.tgt, f.host, f.tparams, f.glm, D, m, x, W->logp.d(), nullptr, st)) return rc;
-  FR_HIP(launch_family_logdensity(f.fam, D, m, lam, f.df, f.t_const, x, W->zz.d(), st));
+  FR_HIP(launch_family_logdensity(f.fam, m, lam, x, W->zz.d(), st));
   hipLaunchKernelGGL(sub_kernel, dim3(blocks(m)), dim3(256), 0, st, m, W->logp.d(), W->zz.d(), lw);
   FR_HIP(hipGetLastError());
   return 0;

@@ -10,6 +10,32 @@ namespace vbk {
 
 constexpr int kBlockDMax = 16;  // largest D handled by the block-per-problem kernel
 
+// The variational family of a call: kind (0 = mf gaussian, 1 = mf t, kFamilyFrT) and
+// the constants that follow from df (check_family in vb_capi.hip).
+struct Family {
+  int kind, D;
+  double df;
+  double t_scale, shape;  // mf t: sqrt(df/2), df/2
+  double t_const;         // log normaliser of the t density (per coordinate / multivariate)
+};
+
+// Where a launch takes its standardized draws from: host-generated draws already in
+// device memory (eps), or Philox counters.  Launch functions unpack it into the
+// kernels' own arguments (Rng, step).
+struct Noise {
+  const double* eps;  // null: Philox
+  uint32_t k0, k1, stream;
+  uint32_t stride;    // problem q draws from stream + q * stride
+  long long step;     // step counter of the first step (the kernels use its low 32 bits)
+  // the same source for problem q, k steps on (eps is the caller's to move)
+  Noise at(long long q, long long k) const {
+    Noise n = *this;
+    n.stream += (uint32_t)q * stride;
+    n.step += k;
+    return n;
+  }
+};
+
 // learning_rate_schedule (vb.py:324-342) evaluated on the device for local step i.
 // a, b, start, end are computed on the host with the reference's own float
 // expression order; device fp64 division is IEEE, so lr(i) matches bit for bit.
@@ -83,10 +109,8 @@ bool target_separable(int tgt);
 // n_problems problems, [q][s][N][D], bit-identical to the block kernel's own
 // Philox draws (same counters: pair, sample, rng_step0 + s, stream + q * stride),
 // and, when lq is non-null, each sample's log q partial sum [q][s][N].
-hipError_t launch_block_predraw(int fam, int D, int N, int n_steps, int n_problems, uint32_t k0,
-                                uint32_t k1, uint32_t stream, uint32_t stride,
-                                long long rng_step0, double t_scale, double shape, double df,
-                                double t_const, double* noise, double* lq, hipStream_t s);
+hipError_t launch_block_predraw(const Family& f, int N, int n_steps, int n_problems,
+                                const Noise& nz, double* noise, double* lq, hipStream_t s);
 
 // values[i] = -(c0 + sum_w vpart[s][w]) for i = step0 + s
 hipError_t launch_sep_values(const double* vpart, int n_steps, int n_waves, double c0,
@@ -97,14 +121,12 @@ hipError_t launch_row_mean(const double* hist, long long rows, long long P, long
 
 // elementwise family helpers
 // Bailey t samples of a mean-field t family (the log-weight draws, vbrng.c family 2)
-hipError_t launch_sample_bailey(int D, long long m, const double* lam, double df, uint32_t k0,
-                                uint32_t k1, uint32_t stream, uint32_t step, double* x,
-                                hipStream_t s);
-hipError_t launch_sample(int fam, int D, long long n, const double* lam, double t_scale,
-                         double shape, const double* noise, uint32_t k0, uint32_t k1,
-                         uint32_t stream, uint32_t step, double* x, hipStream_t s);
-hipError_t launch_family_logdensity(int fam, int D, long long n, const double* lam, double df,
-                                    double t_const, const double* x, double* out, hipStream_t s);
+hipError_t launch_sample_bailey(const Family& f, long long m, const double* lam, const Noise& nz,
+                                double* x, hipStream_t s);
+hipError_t launch_sample(const Family& f, long long n, const double* lam, const Noise& nz,
+                         double* x, hipStream_t s);
+hipError_t launch_family_logdensity(const Family& f, long long n, const double* lam,
+                                    const double* x, double* out, hipStream_t s);
 hipError_t launch_target_logdensity(int tgt, int D, long long n, const double* x, double* out,
                                     double* grad, hipStream_t s);
 // fused materialised step rows (draw, x, target log p + gradient, optional log q)
@@ -112,16 +134,13 @@ hipError_t launch_target_logdensity(int tgt, int D, long long n, const double* x
 // receive mfw_rows_parts(D) chunk partials per row, laid out [part][n].
 bool mfw_rows_fusable(int tgt, int D, long long n);
 int mfw_rows_parts(int D);
-hipError_t launch_mfw_rows(int fam, int tgt, int D, long long n, const double* lam, double t_scale,
-                           double shape, double df, double t_const, bool with_lq,
-                           const double* noise, uint32_t k0, uint32_t k1, uint32_t stream,
-                           uint32_t step, double* x, double* grad, double* logp, double* logq,
+hipError_t launch_mfw_rows(const Family& f, int tgt, long long n, const double* lam, bool with_lq,
+                           const Noise& nz, double* x, double* grad, double* logp, double* logq,
                            hipStream_t s);
-hipError_t launch_log_weights(int fam, int tgt, int D, long long m, const double* lam,
-                              double t_scale, double shape, double df, double t_const,
-                              const double* noise, uint32_t k0, uint32_t k1, uint32_t stream,
-                              uint32_t step, double* lw, double* xs, hipStream_t s, int rows = 1,
-                              uint32_t stride = 0);
+// rows > 1: lam [rows][2 D], lw [rows][m]; row q draws from stream + q * nz.stride
+hipError_t launch_log_weights(const Family& f, int tgt, long long m, const double* lam,
+                              const Noise& nz, double* lw, double* xs, hipStream_t s,
+                              int rows = 1);
 // scale (nullable): [min(step + 1, W)] window scales, oldest first
 hipError_t launch_adagrad_update(long long P, double* lam, const double* g, double* ring, int W,
                                  long long step, double lr, double eps, const double* scale,
@@ -225,9 +244,12 @@ struct FrWork;  // per-context workspace + rocBLAS handle
 FrWork* fr_work_create();
 void fr_work_destroy(FrWork* w);
 
-struct FrSpec {
-  int D, N, tgt, chivi, pd;
-  double df, t_const, alpha;
+// What the full-rank and the materialised mean-field paths evaluate: family, target
+// and objective (N = 0 and no objective flags for log weights).
+struct Spec {
+  Family fam;
+  int N, tgt, chivi, pd;
+  double alpha;
   const double* tparams;  // device; corr_gauss: P*[D][D]; regression: the parameter block
   double tconst;          // corr_gauss log normaliser
   HostTarget host;        // tgt == kTargetCallback
@@ -241,8 +263,8 @@ int fr_sqrt(FrWork* W, int D, const double* lam, hipStream_t st, bool warm = fal
             const void* owner = nullptr, bool ready = false);
 constexpr int kFrNSMax = 40;  // Newton-Schulz iterations launched at most per root
 constexpr int kFrPcgMax = 192; // PCG iterations launched at most per gradient
-int fr_draw(FrWork* W, int D, long long n, double df, const double* host_eps, uint32_t k0,
-            uint32_t k1, uint32_t stream, uint32_t step, const double** s_out,
+// nz.eps (host draws) = [s (n), z (n x D)] on the device
+int fr_draw(FrWork* W, const Family& f, long long n, const Noise& nz, const double** s_out,
             const double** z_out, hipStream_t st);
 int fr_transform(FrWork* W, int D, long long n, const double* mu, const double* s,
                  const double* z, double* x, hipStream_t st);
@@ -261,26 +283,17 @@ struct FrNext {
 // up (non-null, Philox draws): the windowed adagrad step is fused into the last
 // kernel (lam updated in place, ring / history row written; grad keeps only the
 // mean part), and with next->prep the step after it is prepared (FrWork).
-int fr_value_grad(FrWork* W, const FrSpec& f, const double* lam, const double* host_eps,
-                  uint32_t k0, uint32_t k1, uint32_t stream, uint32_t step, double* value,
+int fr_value_grad(FrWork* W, const Spec& f, const double* lam, const Noise& nz, double* value,
                   double* grad, hipStream_t st, bool warm = false,
                   const void* owner = nullptr, const MfUpdate* up = nullptr,
                   const FrNext* next = nullptr);
-int fr_logdensity(FrWork* W, int D, double df, double t_const, const double* lam, const double* x,
-                  long long n, double* out, hipStream_t st);
-int fr_log_weights(FrWork* W, const FrSpec& f, const double* lam, long long m,
-                   const double* host_eps, uint32_t k0, uint32_t k1, uint32_t stream,
-                   uint32_t step, double* lw, double* xs, hipStream_t st);
+int fr_logdensity(FrWork* W, const Family& f, const double* lam, const double* x, long long n,
+                  double* out, hipStream_t st);
+int fr_log_weights(FrWork* W, const Spec& f, const double* lam, long long m, const Noise& nz,
+                   double* lw, double* xs, hipStream_t st);
 int fr_moments(FrWork* W, int D, const double* lam, double* sigma, double* eig, hipStream_t st);
 
 // Mean-field families on the materialised path (any D, any objective / target).
-struct MfSpec {
-  int fam, D, N, tgt, chivi, pd;
-  double alpha, t_scale, shape, df, t_const;
-  HostTarget host;  // tgt == kTargetCallback
-  const double* tparams;  // device; regression: the parameter block
-  GlmHead glm;            // tgt == kTargetRegression
-};
 // Optional windowed-adagrad step fused into the gradient pass (lam updated in
 // place, the step's gradient pushed into ring [W][P], new parameters copied to
 // hrow when non-null); same arithmetic as launch_adagrad_update without scales.
@@ -291,12 +304,10 @@ struct MfUpdate {
   double lr, eps;
   double* hrow;
 };
-int mf_wide_value_grad(FrWork* W, const MfSpec& f, const double* lam, const double* host_eps,
-                       uint32_t k0, uint32_t k1, uint32_t stream, uint32_t step, double* value,
-                       double* grad, hipStream_t st, const MfUpdate* up = nullptr);
-int mf_wide_log_weights(FrWork* W, const MfSpec& f, const double* lam, long long m,
-                        const double* host_eps, uint32_t k0, uint32_t k1, uint32_t stream,
-                        uint32_t step, double* lw, double* xs, hipStream_t st);
+int mf_wide_value_grad(FrWork* W, const Spec& f, const double* lam, const Noise& nz,
+                       double* value, double* grad, hipStream_t st, const MfUpdate* up = nullptr);
+int mf_wide_log_weights(FrWork* W, const Spec& f, const double* lam, long long m, const Noise& nz,
+                        double* lw, double* xs, hipStream_t st);
 // 0, or a VB_E* code with the message set (eigendecomposition / Newton-Schulz /
 // PCG failure since the last call); synchronises the stream.
 // retry (non-null): a warm Newton-Schulz root that did not converge sets *retry,
@@ -317,8 +328,7 @@ int fr_warm_restore(FrWork* W, hipStream_t st);
 // Clears the Newton-Schulz floor a rerun set (the rerun's own warm steps have
 // taught fr_info the count they need).
 void fr_retry_done(FrWork* W);
-hipError_t launch_fr_lw(int D, long long m, double df, double t_const, const double* logp,
-                        const double* zz, const double* s, const double* scal, double* lw,
-                        hipStream_t st);
+hipError_t launch_fr_lw(const Family& f, long long m, const double* logp, const double* zz,
+                        const double* s, const double* scal, double* lw, hipStream_t st);
 
 }  // namespace vbk

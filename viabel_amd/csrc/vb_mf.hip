@@ -1955,19 +1955,19 @@ __global__ __launch_bounds__(256) void block_predraw_kernel(int D, int N, int n_
   if (lq) lq[idx] = lqs;
 }
 
-hipError_t launch_block_predraw(int fam, int D, int N, int n_steps, int nprob, uint32_t k0,
-                                uint32_t k1, uint32_t stream, uint32_t stride, long long rng_step0,
-                                double t_scale, double shape, double df, double t_const,
+hipError_t launch_block_predraw(const Family& f, int N, int n_steps, int nprob, const Noise& nz,
                                 double* noise, double* lq, hipStream_t s) {
   const long long total = (long long)nprob * n_steps * N;
   if (total <= 0) return hipSuccess;
   const dim3 grid((unsigned)((total + 255) / 256));
-  if (fam == 1)
-    hipLaunchKernelGGL(block_predraw_kernel<true>, grid, dim3(256), 0, s, D, N, n_steps, total, k0,
-                       k1, stream, stride, rng_step0, t_scale, shape, df, t_const, noise, lq);
+  if (f.kind == 1)
+    hipLaunchKernelGGL(block_predraw_kernel<true>, grid, dim3(256), 0, s, f.D, N, n_steps, total,
+                       nz.k0, nz.k1, nz.stream, nz.stride, nz.step, f.t_scale, f.shape, f.df,
+                       f.t_const, noise, lq);
   else
-    hipLaunchKernelGGL(block_predraw_kernel<false>, grid, dim3(256), 0, s, D, N, n_steps, total, k0,
-                       k1, stream, stride, rng_step0, t_scale, shape, df, t_const, noise, lq);
+    hipLaunchKernelGGL(block_predraw_kernel<false>, grid, dim3(256), 0, s, f.D, N, n_steps, total,
+                       nz.k0, nz.k1, nz.stream, nz.stride, nz.step, f.t_scale, f.shape, f.df,
+                       f.t_const, noise, lq);
   return hipGetLastError();
 }
 
@@ -2621,22 +2621,23 @@ hipError_t launch_row_mean(const double* hist, long long rows, long long P, long
   return hipGetLastError();
 }
 
-hipError_t launch_sample(int fam, int D, long long n, const double* lam, double t_scale,
-                         double shape, const double* noise, uint32_t k0, uint32_t k1,
-                         uint32_t stream, uint32_t step, double* x, hipStream_t s) {
+hipError_t launch_sample(const Family& f, long long n, const double* lam, const Noise& nz,
+                         double* x, hipStream_t s) {
+  const int D = f.D;
   const long long tot = n * ((D + 1) / 2);
   if (tot == 0) return hipSuccess;
   const dim3 grid((unsigned)((tot + 255) / 256)), block(256);
-  const Rng rng{k0, k1, stream};
-  if (noise)
-    hipLaunchKernelGGL((sample_kernel<false, true>), grid, block, 0, s, D, n, lam, t_scale, shape,
-                       noise, rng, step, x);
-  else if (fam == 1)
-    hipLaunchKernelGGL((sample_kernel<true, false>), grid, block, 0, s, D, n, lam, t_scale, shape,
-                       noise, rng, step, x);
+  const Rng rng{nz.k0, nz.k1, nz.stream};
+  const uint32_t step = (uint32_t)nz.step;
+  if (nz.eps)
+    hipLaunchKernelGGL((sample_kernel<false, true>), grid, block, 0, s, D, n, lam, f.t_scale,
+                       f.shape, nz.eps, rng, step, x);
+  else if (f.kind == 1)
+    hipLaunchKernelGGL((sample_kernel<true, false>), grid, block, 0, s, D, n, lam, f.t_scale,
+                       f.shape, nz.eps, rng, step, x);
   else
-    hipLaunchKernelGGL((sample_kernel<false, false>), grid, block, 0, s, D, n, lam, t_scale,
-                       shape, noise, rng, step, x);
+    hipLaunchKernelGGL((sample_kernel<false, false>), grid, block, 0, s, D, n, lam, f.t_scale,
+                       f.shape, nz.eps, rng, step, x);
   return hipGetLastError();
 }
 
@@ -2663,14 +2664,13 @@ __global__ __launch_bounds__(256) void sample_bailey_kernel(int D, long long n, 
   if (2 * j + 1 < D) x[r * D + 2 * j + 1] = tb * exp(lam[D + 2 * j + 1]) + lam[2 * j + 1];
 }
 
-hipError_t launch_sample_bailey(int D, long long m, const double* lam, double df, uint32_t k0,
-                                uint32_t k1, uint32_t stream, uint32_t step, double* x,
-                                hipStream_t s) {
-  const long long tot = m * ((D + 1) / 2);
+hipError_t launch_sample_bailey(const Family& f, long long m, const double* lam, const Noise& nz,
+                                double* x, hipStream_t s) {
+  const long long tot = m * ((f.D + 1) / 2);
   if (tot == 0) return hipSuccess;
-  const Rng rng{k0, k1, stream};
-  hipLaunchKernelGGL(sample_bailey_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, D,
-                     m, lam, df, rng, step, x);
+  const Rng rng{nz.k0, nz.k1, nz.stream};
+  hipLaunchKernelGGL(sample_bailey_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s,
+                     f.D, m, lam, f.df, rng, (uint32_t)nz.step, x);
   return hipGetLastError();
 }
 
@@ -2802,50 +2802,44 @@ __global__ __launch_bounds__(256) void mfw_rows_kernel(int D, long long n, const
 }
 
 template <class TGT>
-static void mfw_rows_dispatch(int fam, int D, long long n, const double* lam, double t_scale,
-                              double shape, double df, double t_const, bool with_lq,
-                              const double* noise, const Rng& rng, uint32_t step, double* x,
-                              double* grad, double* logp, double* logq, hipStream_t s) {
+static void mfw_rows_dispatch(const Family& f, long long n, const double* lam, bool with_lq,
+                              const Noise& nz, double* x, double* grad, double* logp,
+                              double* logq, hipStream_t s) {
+  const int D = f.D;
   const dim3 g((unsigned)mfw_rows_parts(D), (unsigned)((n + kRowsPerBlock - 1) / kRowsPerBlock)),
       b(256);
   const int wl = with_lq ? 1 : 0;
-  if (noise && fam == 1)
-    hipLaunchKernelGGL((mfw_rows_kernel<TGT, true, true>), g, b, 0, s, D, n, lam, t_scale, shape,
-                       df, t_const, wl, noise, rng, step, x, grad, logp, logq);
-  else if (noise)
-    hipLaunchKernelGGL((mfw_rows_kernel<TGT, false, true>), g, b, 0, s, D, n, lam, t_scale, shape,
-                       df, t_const, wl, noise, rng, step, x, grad, logp, logq);
-  else if (fam == 1)
-    hipLaunchKernelGGL((mfw_rows_kernel<TGT, true, false>), g, b, 0, s, D, n, lam, t_scale, shape,
-                       df, t_const, wl, noise, rng, step, x, grad, logp, logq);
-  else
-    hipLaunchKernelGGL((mfw_rows_kernel<TGT, false, false>), g, b, 0, s, D, n, lam, t_scale, shape,
-                       df, t_const, wl, noise, rng, step, x, grad, logp, logq);
+  const Rng rng{nz.k0, nz.k1, nz.stream};
+  const uint32_t step = (uint32_t)nz.step;
+#define VB_MFW_ROWS(TFAM, HOST)                                                              \
+  hipLaunchKernelGGL((mfw_rows_kernel<TGT, TFAM, HOST>), g, b, 0, s, D, n, lam, f.t_scale,  \
+                     f.shape, f.df, f.t_const, wl, nz.eps, rng, step, x, grad, logp, logq)
+  if (nz.eps && f.kind == 1) VB_MFW_ROWS(true, true);
+  else if (nz.eps) VB_MFW_ROWS(false, true);
+  else if (f.kind == 1) VB_MFW_ROWS(true, false);
+  else VB_MFW_ROWS(false, false);
+#undef VB_MFW_ROWS
 }
 
 bool mfw_rows_fusable(int tgt, int D, long long n) {
   return (tgt == 0 || tgt == 1) && D >= kWideRowD && n >= 1 && n <= 65535;
 }
 
-hipError_t launch_mfw_rows(int fam, int tgt, int D, long long n, const double* lam, double t_scale,
-                           double shape, double df, double t_const, bool with_lq,
-                           const double* noise, uint32_t k0, uint32_t k1, uint32_t stream,
-                           uint32_t step, double* x, double* grad, double* logp, double* logq,
+hipError_t launch_mfw_rows(const Family& f, int tgt, long long n, const double* lam, bool with_lq,
+                           const Noise& nz, double* x, double* grad, double* logp, double* logq,
                            hipStream_t s) {
-  if (!mfw_rows_fusable(tgt, D, n)) return hipErrorInvalidValue;
-  const Rng rng{k0, k1, stream};
+  if (!mfw_rows_fusable(tgt, f.D, n)) return hipErrorInvalidValue;
   if (tgt == 0)
-    mfw_rows_dispatch<IsoGauss>(fam, D, n, lam, t_scale, shape, df, t_const, with_lq, noise, rng,
-                                step, x, grad, logp, logq, s);
+    mfw_rows_dispatch<IsoGauss>(f, n, lam, with_lq, nz, x, grad, logp, logq, s);
   else
-    mfw_rows_dispatch<Mixture>(fam, D, n, lam, t_scale, shape, df, t_const, with_lq, noise, rng,
-                               step, x, grad, logp, logq, s);
+    mfw_rows_dispatch<Mixture>(f, n, lam, with_lq, nz, x, grad, logp, logq, s);
   return hipGetLastError();
 }
 
-hipError_t launch_family_logdensity(int fam, int D, long long n, const double* lam, double df,
-                                    double t_const, const double* x, double* out,
-                                    hipStream_t s) {
+hipError_t launch_family_logdensity(const Family& f, long long n, const double* lam,
+                                    const double* x, double* out, hipStream_t s) {
+  const int fam = f.kind, D = f.D;
+  const double df = f.df, t_const = f.t_const;
   if (n == 0) return hipSuccess;
   if (D >= kWideRowD && n <= 65535) {
     if (fam == 1)
@@ -2899,14 +2893,17 @@ hipError_t launch_target_logdensity(int tgt, int D, long long n, const double* x
 }
 
 template <class TGT, bool TFAM, bool HOST>
-static void logw_launch(int D, long long m, const double* lam, double t_scale, double shape,
-                        double df, double t_const, const double* noise, Rng rng, uint32_t step,
-                        int rows, uint32_t stride, double* lw, double* xs, hipStream_t s) {
+static void logw_launch(const Family& f, long long m, const double* lam, const Noise& nz, int rows,
+                        double* lw, double* xs, hipStream_t s) {
+  const int D = f.D;
+  const Rng rng{nz.k0, nz.k1, nz.stream};
+  const uint32_t step = (uint32_t)nz.step;
   if constexpr (TGT::kSeparable) {
     if (D > kBlockDMax) {
       hipLaunchKernelGGL((logw_sep_kernel<TGT, TFAM, HOST>),
                          dim3((unsigned)((m + 3) / 4), (unsigned)rows), dim3(256), 0, s, D, m,
-                         lam, t_scale, shape, df, t_const, noise, rng, step, stride, lw, xs);
+                         lam, f.t_scale, f.shape, f.df, f.t_const, nz.eps, rng, step, nz.stride,
+                         lw, xs);
       return;
     }
   }
@@ -2915,7 +2912,7 @@ static void logw_launch(int D, long long m, const double* lam, double t_scale, d
     const dim3 g((unsigned)((m + 255) / 256), (unsigned)rows);
 #define VB_LOGW(DM)                                                                            \
   hipLaunchKernelGGL((logw_row_kernel<TGT, TFAM, HOST, DM>), g, dim3(256), 0, s, D, m, lam,   \
-                     t_scale, shape, df, t_const, noise, rng, step, stride, lw, xs)
+                     f.t_scale, f.shape, f.df, f.t_const, nz.eps, rng, step, nz.stride, lw, xs)
     if (D <= 2) VB_LOGW(2);
     else if (D <= 4) VB_LOGW(4);
     else if (D <= 10) VB_LOGW(10);
@@ -2925,32 +2922,25 @@ static void logw_launch(int D, long long m, const double* lam, double t_scale, d
 }
 
 template <class TGT>
-static void logw_fam(int fam, bool host, int D, long long m, const double* lam, double t_scale,
-                     double shape, double df, double t_const, const double* noise, Rng rng,
-                     uint32_t step, int rows, uint32_t stride, double* lw, double* xs,
-                     hipStream_t s) {
-  if (fam == 1) {
-    if (host) logw_launch<TGT, true, true>(D, m, lam, t_scale, shape, df, t_const, noise, rng, step, rows, stride, lw, xs, s);
-    else logw_launch<TGT, true, false>(D, m, lam, t_scale, shape, df, t_const, noise, rng, step, rows, stride, lw, xs, s);
+static void logw_fam(const Family& f, long long m, const double* lam, const Noise& nz, int rows,
+                     double* lw, double* xs, hipStream_t s) {
+  if (f.kind == 1) {
+    if (nz.eps) logw_launch<TGT, true, true>(f, m, lam, nz, rows, lw, xs, s);
+    else logw_launch<TGT, true, false>(f, m, lam, nz, rows, lw, xs, s);
   } else {
-    if (host) logw_launch<TGT, false, true>(D, m, lam, t_scale, shape, df, t_const, noise, rng, step, rows, stride, lw, xs, s);
-    else logw_launch<TGT, false, false>(D, m, lam, t_scale, shape, df, t_const, noise, rng, step, rows, stride, lw, xs, s);
+    if (nz.eps) logw_launch<TGT, false, true>(f, m, lam, nz, rows, lw, xs, s);
+    else logw_launch<TGT, false, false>(f, m, lam, nz, rows, lw, xs, s);
   }
 }
 
-hipError_t launch_log_weights(int fam, int tgt, int D, long long m, const double* lam,
-                              double t_scale, double shape, double df, double t_const,
-                              const double* noise, uint32_t k0, uint32_t k1, uint32_t stream,
-                              uint32_t step, double* lw, double* xs, hipStream_t s, int rows,
-                              uint32_t stride) {
+hipError_t launch_log_weights(const Family& f, int tgt, long long m, const double* lam,
+                              const Noise& nz, double* lw, double* xs, hipStream_t s, int rows) {
   if (m == 0 || rows <= 0) return hipSuccess;
-  const Rng rng{k0, k1, stream};
-  const bool host = noise != nullptr;
   switch (tgt) {
-    case 0: logw_fam<IsoGauss>(fam, host, D, m, lam, t_scale, shape, df, t_const, noise, rng, step, rows, stride, lw, xs, s); break;
-    case 1: logw_fam<Mixture>(fam, host, D, m, lam, t_scale, shape, df, t_const, noise, rng, step, rows, stride, lw, xs, s); break;
-    case 2: logw_fam<Funnel>(fam, host, D, m, lam, t_scale, shape, df, t_const, noise, rng, step, rows, stride, lw, xs, s); break;
-    case 3: logw_fam<EightSchools>(fam, host, D, m, lam, t_scale, shape, df, t_const, noise, rng, step, rows, stride, lw, xs, s); break;
+    case 0: logw_fam<IsoGauss>(f, m, lam, nz, rows, lw, xs, s); break;
+    case 1: logw_fam<Mixture>(f, m, lam, nz, rows, lw, xs, s); break;
+    case 2: logw_fam<Funnel>(f, m, lam, nz, rows, lw, xs, s); break;
+    case 3: logw_fam<EightSchools>(f, m, lam, nz, rows, lw, xs, s); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
