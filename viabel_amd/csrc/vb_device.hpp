@@ -38,9 +38,15 @@ __device__ __forceinline__ u4 philox(uint32_t c0, uint32_t c1, uint32_t c2, uint
     }
     const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
     const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-    // three-input XOR in one v_bitop3_b32 (gfx950, truth table 0x96)
-    const uint32_t n0 = __builtin_amdgcn_bitop3_b32((uint32_t)(p1 >> 32), c1, k0, 0x96);
-    const uint32_t n2 = __builtin_amdgcn_bitop3_b32((uint32_t)(p0 >> 32), c3, k1, 0x96);
+    // three-input XOR in one v_bitop3_b32 (gfx950, truth table 0x96).  Round 0 pairs
+    // the operands that are uniform over a wave in the column-pair kernel first (the
+    // step's product with the key; the stream word with the key): those XORs are scalar
+    // and leave the round one two-operand vector XOR each, where the three-input form
+    // with two scalar operands costs a v_mov first (one scalar operand per VALU)
+    const uint32_t n0 = r ? __builtin_amdgcn_bitop3_b32((uint32_t)(p1 >> 32), c1, k0, 0x96)
+                          : c1 ^ ((uint32_t)(p1 >> 32) ^ k0);
+    const uint32_t n2 = r ? __builtin_amdgcn_bitop3_b32((uint32_t)(p0 >> 32), c3, k1, 0x96)
+                          : (uint32_t)(p0 >> 32) ^ (c3 ^ k1);
     c1 = (uint32_t)p1;
     c3 = (uint32_t)p0;
     c0 = n0;
@@ -300,7 +306,9 @@ __device__ __forceinline__ double log_u01_tab(double u, const double2* ltab) {
   // j = rint(256 m) - 128 in [0, 128] (= rint(256 m - 128): the shift is an even
   // integer); 256 m by ldexp, the -128 folded into the LDS read offset (an fma
   // needed its two constants in VGPRs, re-made every call)
-  const double2 t = ltab[kLogN - 128 + (int)rint(ldexp(m, 8))];
+  // rint and the conversion in one add: 256 m + 1.5 2^52 rounds to an integer to nearest
+  // even, as rint does, and its low word is that integer (<= 256)
+  const double2 t = ltab[kLogN - 128 + __double2loint(ldexp(m, 8) + 0x1.8p52)];
   const double r = fma(m, t.x, -1.0);
   double p = 0.14285714285714285;                // 1/7
   p = hfma(p, r, -0.16666666666666666);
@@ -322,6 +330,28 @@ __device__ __forceinline__ void sincospi_tab(double x, double& sn, double& cs,
   const double r = fma(q, -0.0078125, x);           // exact
   const double2 t = sct[(int)q];
   const double th = fma(r, 3.141592653589793, r * 1.2246467991473532e-16);
+  const double t2 = th * th;
+  double ps = hfma(t2, -0.0001984126984126984, 0.008333333333333333);
+  ps = hfma(ps, t2, -0.16666666666666666);
+  const double st = fma(th * t2, ps, th);           // sin(theta)
+  double pc = hfma(t2, 2.48015873015873e-05, -0.001388888888888889);
+  pc = hfma(pc, t2, 0.041666666666666664);
+  pc = hfma(pc, t2, -0.5);
+  const double ct = fma(t2, pc, 1.0);               // cos(theta)
+  sn = fma(t.x, ct, t.y * st);
+  cs = fma(t.y, ct, -(t.x * st));
+}
+
+// sincospi_tab(2 u, ...) for u in [0, 1) (Box-Muller's angle) from u itself: q and theta
+// are those of sincospi_tab at x = 2 u bit for bit -- q = rint(256 u) = rint(128 x); the
+// residual is r = x_r / 2 exactly, and theta takes it with the doubled pi constants (both
+// products and the fma round the same real numbers) -- without the doubling of u.
+__device__ __forceinline__ void sincos2pi_tab(double u, double& sn, double& cs,
+                                              const double2* sct) {
+  const double q = rint(ldexp(u, 8));               // 0..256
+  const double r = fma(q, -0.00390625, u);          // exact
+  const double2 t = sct[(int)q];
+  const double th = fma(r, 6.283185307179586, r * 2.4492935982947064e-16);
   const double t2 = th * th;
   double ps = hfma(t2, -0.0001984126984126984, 0.008333333333333333);
   ps = hfma(ps, t2, -0.16666666666666666);
@@ -362,8 +392,9 @@ __device__ __forceinline__ void normal_pair_tab(u4 w, double& z0, double& z1, co
 //   u1 = 1.m - (1 - 2^-53) = (2m + 1) 2^-53  in (0, 1)   (never 0: log is finite)
 //   u2 = 1.m - 1            = m 2^-52         in [0, 1)
 __device__ __forceinline__ double unit_mantissa(uint32_t lo, uint32_t hi) {
+  // both words are one v_alignbit_b32: the high one shifts the exponent 0x3FF in over hi
   const uint32_t mlo = __builtin_amdgcn_alignbit(hi, lo, 12);
-  const uint32_t mhi = (hi >> 12) | 0x3FF00000u;
+  const uint32_t mhi = __builtin_amdgcn_alignbit(0x3FFu, hi, 12);
   return __hiloint2double((int)mhi, (int)mlo);
 }
 
@@ -373,7 +404,7 @@ __device__ __forceinline__ void normal_pair_tab(u4 w, double& z0, double& z1, co
   const double u2 = unit_mantissa(w.z, w.w) - 1.0;
   const double r = sqrt_pos(-2.0 * log_u01_tab(u1, ltab));
   double s, c;
-  sincospi_tab(2.0 * u2, s, c, sct);
+  sincos2pi_tab(u2, s, c, sct);
   z0 = r * c;
   z1 = r * s;
 }

@@ -105,6 +105,14 @@ __device__ __forceinline__ double reduce4(int lane, double q0, double q1, double
   }
 }
 
+// acc + t^2 in two roundings: contraction is off for the statement (the rounded-
+// operation intrinsics are plain operators to the compiler, which fuses them)
+__device__ __forceinline__ double add_square_2r(double acc, double t) {
+#pragma clang fp contract(off)
+  const double p = t * t;
+  return acc + p;
+}
+
 // Sum over the lanes that hold one parameter's window slots: the 16 lanes of
 // its row (PPW == 1) or the residue class l & 3 of its group (PPW >= 2).
 template <int PPW>
@@ -355,7 +363,12 @@ __device__ __forceinline__ void sep_body(const SepArgs& a, double* ring_base, in
     v3 = v2;
     v2 = v1;
     v1 = v0;
-    v0 = ent ? fma(v, invN, lam_own) : v * invN;
+    // one fma for both kinds of lane: off the entropy lanes the addend +0 leaves the
+    // rounded product, but for a -0 product (the isotropic target's lanes without a row),
+    // which becomes +0.  No written total sees that: a zero only changes a sum of zeros,
+    // and every pair's sum includes lane gl = 0, a mean lane with a row, whose partial
+    // is finite and nonzero or the total is not finite either way.
+    v0 = fma(v, invN, ent ? lam_own : 0.0);
     if ((s & 3) == 3 || s + 1 == a.n_steps) {
       const double tot = reduce4<PPW>(lane, v3, v2, v1, v0);  // owner q: step s - 3 + q
       const int st = s - 3 + own;
@@ -382,8 +395,10 @@ __device__ __forceinline__ void sep_body(const SepArgs& a, double* ring_base, in
       for (int j = 0; j < PPW; ++j) {
         const int sl = j * SL + sub;
         if (sl == slot) rg[j] = g_own;
-        const double t = rg[j];
-        acc += (sl < W) ? t * t : 0.0;
+        // no sl < W guard: a slot at or past W holds 0 for good (rg starts at 0, is
+        // loaded only below W and written only at sl == slot < W).  Product and sum
+        // round separately, as the guarded form did (add_square_2r).
+        acc = add_square_2r(acc, rg[j]);
       }
       q = owner_sum<PPW>(acc);
     } else {
