@@ -87,8 +87,10 @@ enum vb_target_kind {
   VB_TARGET_CALLBACK = 5,     /* user model through vb_target.callback (make_stan_log_density,
                                  vb.py:314-321): evaluated on the host once per step on the
                                  batch of samples; everything else stays on the device */
-  VB_TARGET_REGRESSION = 6    /* generalised linear model over a data matrix in `params`
+  VB_TARGET_REGRESSION = 6,   /* generalised linear model over a data matrix in `params`
                                  (layout below), evaluated on the device; any family, any D */
+  VB_TARGET_HIERARCHICAL = 7  /* hierarchical normal means over J groups in `params` (layout
+                                 below), centred or non-centred; any family, D = J + 2 */
 };
 
 /* VB_TARGET_REGRESSION: log p(beta) = sum_d log N(beta_d; 0, s^2) + sum_m l(y_m, eta_m),
@@ -108,6 +110,24 @@ enum vb_target_kind {
  *   n_params = 8 + M*D + M
  * vb_run_create copies the block once into the run; one-shot calls stage a host
  * block per call and read a device block in place. */
+
+/* VB_TARGET_HIERARCHICAL: J groups with data y_j and sigma_j > 0, unconstrained
+ * x = [mu, u = log tau, then J more], dim = J + 2; Stan's log_prob convention (constants
+ * of the ~ statements dropped, the Jacobian term +u kept), tau = exp(u):
+ *   common       -(mu / s_mu)^2 / 2 - log1p((tau / s_tau)^2) + u
+ *   non-centred  - sum th_j^2 / 2 - sum ((y_j - mu - tau th_j) / sigma_j)^2 / 2
+ *   centred      - J u - sum ((th_j - mu) / tau)^2 / 2 - sum ((y_j - th_j) / sigma_j)^2 / 2
+ * vb_target.params (host or device memory):
+ *   params[0] form: 0 non-centred, 1 centred
+ *   params[1] J (number of groups, >= 1, integral)
+ *   params[2] s_mu  (> 0): mu ~ N(0, s_mu^2)
+ *   params[3] s_tau (> 0): tau ~ half-Cauchy(0, s_tau)
+ *   params[4..7] reserved, zero
+ *   params[8 ..]      y [J]
+ *   params[8 + J ..]  sigma [J]
+ *   n_params = 8 + 2 J
+ * With the eight-schools data and s_mu = s_tau = 5 the non-centred form is
+ * VB_TARGET_EIGHT_SCHOOLS_NCP's density.  Staged and copied as the regression block is. */
 
 /* User target: log p and d log p / dx of the n rows of x [n][d] (HOST memory,
  * C order) into logp [n] and grad [n][d]; return 0, or non-zero to abort the

@@ -1,0 +1,94 @@
+"""Step time of adagrad_optimize for one hierarchical normal-means model evaluated
+two ways: through targets.callback (the numpy restatement, on the host once per step)
+and through targets.hierarchical_normal (on the device).  Prints one JSON line per
+case.
+
+  case i   J = 8 (eight schools), N = 100, mean-field t, centred
+  case ii  J = 10 000,            N = 128, mean-field Gaussian, non-centred
+
+Each timing is a whole adagrad_optimize call of --steps iterations divided by the
+step count; the device is synchronised before both clocks; --warmup untimed calls,
+then the median of --reps.  --device-only skips the callback path (for a kernel
+trace of the device path alone).
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from tests import hier_cases as hc  # noqa: E402
+
+CASES = {
+    'i': dict(J=8, N=100, family='mf_t', df=40.0, centered=True, steps=200),
+    'ii': dict(J=10000, N=128, family='mf_gauss', df=None, centered=False, steps=50),
+}
+
+
+def _time(fn, sync, warmup, reps):
+    for _ in range(warmup):
+        fn()
+    out = []
+    for _ in range(reps):
+        sync()
+        t0 = time.perf_counter()
+        fn()
+        sync()
+        out.append(time.perf_counter() - t0)
+    return out
+
+
+def run_case(name, steps, warmup, reps, device_only):
+    from viabel_amd import vb, targets, _native as nat
+    c = CASES[name]
+    J, N = c['J'], c['N']
+    D = J + 2
+    steps = steps or c['steps']
+    if name == 'i':
+        y, sigma = np.array(hc.ES_Y), np.array(hc.ES_SIGMA)
+    else:
+        y, sigma = hc.make_data(J, 1)
+
+    def family():
+        if c['family'] == 'mf_t':
+            return vb.mean_field_t_variational_family(D, c['df'], rng='numpy')
+        return vb.mean_field_gaussian_variational_family(D, rng='numpy')
+
+    init = np.zeros(2 * D)
+    sync = nat.context().synchronize
+    paths = {'device': targets.hierarchical_normal(y, sigma, centered=c['centered'])}
+    if not device_only:
+        paths['callback'] = targets.callback(hc.restatement(y, sigma, c['centered']), D)
+    res = dict(case=name, J=J, D=D, N=N, family=c['family'], centered=c['centered'], steps=steps,
+               warmup=warmup, reps=reps)
+    for label, tgt in paths.items():
+        obj = vb.black_box_klvi(family(), tgt, N)
+        ts = _time(lambda: vb.adagrad_optimize(steps, obj, init), sync, warmup, reps)
+        res[label + '_us_per_step'] = 1e6 * statistics.median(ts) / steps
+        res[label + '_us_per_step_all'] = [round(1e6 * t / steps, 2) for t in ts]
+    if not device_only:
+        res['callback_over_device'] = res['callback_us_per_step'] / res['device_us_per_step']
+    print(json.dumps(res), flush=True)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--case', default='all', choices=['all', 'i', 'ii'])
+    ap.add_argument('--steps', type=int, default=0, help='iterations per call (0: the case default)')
+    ap.add_argument('--warmup', type=int, default=2)
+    ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--device-only', action='store_true')
+    a = ap.parse_args()
+    for name in (['i', 'ii'] if a.case == 'all' else [a.case]):
+        run_case(name, a.steps, a.warmup, a.reps, a.device_only)
+
+
+if __name__ == '__main__':
+    main()

@@ -590,9 +590,58 @@ int regression_head(const vb_target* t, vbk::GlmHead* o) {
   return VB_OK;
 }
 
-int check_target(const vb_target* t, int D, vbk::GlmHead* glm = nullptr) {
+// Header of a hierarchical target's parameter block (include/viabel_amd.h), read from
+// host or device memory and checked against n_params and dim.
+int hierarchical_head(const vb_target* t, vbk::HierHead* o) {
+  if (!t->params || t->n_params < vbk::kHierHeader)
+    return fail(VB_EINVAL, "hierarchical target: n_params %lld is shorter than the %d-value header",
+                (long long)t->n_params, vbk::kHierHeader);
+  double h[vbk::kHierHeader];
+  const int pc = ptr_class(t->params);
+  if (pc < 0) return foreign_ptr_error(t->params);
+  if (pc == 1)
+    VB_HIP(hipMemcpy(h, t->params, sizeof h, hipMemcpyDeviceToHost));
+  else
+    std::memcpy(h, t->params, sizeof h);
+  if (!(h[0] == 0.0 || h[0] == 1.0))
+    return fail(VB_EINVAL, "hierarchical target: params[0] (form) must be 0 or 1, got %g", h[0]);
+  if (!(h[1] >= 1.0 && h[1] <= 2.0e9 && h[1] == std::floor(h[1])))
+    return fail(VB_EINVAL, "hierarchical target: params[1] (J) must be an integer >= 1, got %g", h[1]);
+  if (!(h[2] > 0.0 && std::isfinite(h[2])))
+    return fail(VB_EINVAL, "hierarchical target: params[2] (mu_scale) must be positive, got %g", h[2]);
+  if (!(h[3] > 0.0 && std::isfinite(h[3])))
+    return fail(VB_EINVAL, "hierarchical target: params[3] (tau_scale) must be positive, got %g", h[3]);
+  for (int i = 4; i < vbk::kHierHeader; ++i)
+    if (h[i] != 0.0)
+      return fail(VB_EINVAL, "hierarchical target: params[%d] (reserved) must be zero, got %g", i, h[i]);
+  const double want = (double)vbk::kHierHeader + 2.0 * h[1];
+  if ((double)t->n_params != want)
+    return fail(VB_EINVAL, "hierarchical target: n_params %lld does not match 8 + 2*J = %.0f (J %.0f)",
+                (long long)t->n_params, want, h[1]);
+  if ((double)t->dim != h[1] + 2.0)
+    return fail(VB_EINVAL, "hierarchical target: dim %lld does not match J + 2 = %.0f",
+                (long long)t->dim, h[1] + 2.0);
+  o->centered = (int)h[0];
+  o->J = (long long)h[1];
+  o->mu_scale = h[2];
+  o->tau_scale = h[3];
+  return VB_OK;
+}
+
+// Host copies of the headers of the targets that carry a parameter block.
+struct TargetHeads {
+  vbk::GlmHead glm{};
+  vbk::HierHead hier{};
+};
+
+// Whether the target's `params` is a block used whole (regression, hierarchical).
+bool block_target(int kind) {
+  return kind == VB_TARGET_REGRESSION || kind == VB_TARGET_HIERARCHICAL;
+}
+
+int check_target(const vb_target* t, int D, TargetHeads* heads = nullptr) {
   if (!t) return fail(VB_EINVAL, "null vb_target");
-  if (t->kind < VB_TARGET_ISOGAUSS || t->kind > VB_TARGET_REGRESSION)
+  if (t->kind < VB_TARGET_ISOGAUSS || t->kind > VB_TARGET_HIERARCHICAL)
     return fail(VB_EUNSUPPORTED, "target kind %d is not implemented on the device", t->kind);
   if (t->kind == VB_TARGET_CALLBACK && !t->callback)
     return fail(VB_EINVAL, "callback target needs a callback");
@@ -608,7 +657,12 @@ int check_target(const vb_target* t, int D, vbk::GlmHead* glm = nullptr) {
   if (t->kind == VB_TARGET_REGRESSION) {
     vbk::GlmHead h{};
     VB_TRY(regression_head(t, &h));
-    if (glm) *glm = h;
+    if (heads) heads->glm = h;
+  }
+  if (t->kind == VB_TARGET_HIERARCHICAL) {
+    vbk::HierHead h{};
+    VB_TRY(hierarchical_head(t, &h));
+    if (heads) heads->hier = h;
   }
   return VB_OK;
 }
@@ -625,13 +679,13 @@ vbk::Noise noise_of(const vb_noise* n, const double* eps) {
 constexpr int kSlotRunTparams = 1;  // vb_run_create: copied into the run; init then takes 0
 constexpr int kSlotTparams = 3;     // corr_gauss: lam, draws, gradient in 0-2, the value in 4
 constexpr int kSlotTparamsLw = 4;   // corr_gauss in vb_log_weights, whose samples take 3
-constexpr int kSlotGlm = 8;         // regression block: the mean-field calls use all of 0-7
+constexpr int kSlotGlm = 8;         // parameter block (block_target): the mean-field calls use 0-7
 
 // Device copy of a target's parameters and its scalar log normaliser.
 int target_params(vb_ctx* c, int s, const vb_target* t, const double** dev, double* tconst) {
   *dev = nullptr;
   *tconst = 0.0;
-  if (t->kind == VB_TARGET_REGRESSION) {   // the whole block; a device pointer is used in place
+  if (block_target(t->kind)) {   // the whole block; a device pointer is used in place
     In in;
     VB_TRY(in.stage(c, s, t->params, (size_t)t->n_params));
     *dev = in.d;
@@ -690,9 +744,10 @@ int choose_path(const PathFacts& f, Path* out) {
   // CHIVI's weights couple all coordinates of a sample: no column-pair kernel
   const bool pairs = wide && vbk::target_separable(f.tgt) && f.obj != VB_OBJ_CHIVI;
   // the column-pair kernel has adagrad only, and both fused kernels keep its window
-  // on chip (<= 64 steps); host callbacks and regression blocks have no fused kernel
+  // on chip (<= 64 steps); host callbacks and the targets with a parameter block have
+  // no fused kernel
   const bool ia = f.opt != VB_OPT_ADAGRAD;
-  const bool materialised = f.tgt == VB_TARGET_CALLBACK || f.tgt == VB_TARGET_REGRESSION ||
+  const bool materialised = f.tgt == VB_TARGET_CALLBACK || block_target(f.tgt) ||
                             (wide && (!pairs || ia)) || (!ia && f.window > 64);
   if (pairs && f.nprob != 1)
     return fail(VB_EUNSUPPORTED, "wide (D > %d) runs hold one problem per vb_run", vbk::kBlockDMax);
@@ -711,7 +766,7 @@ vbk::HostTarget host_of(const vb_target* t) {
 
 // obj null: log weights (no sample count, no objective flags)
 vbk::Spec make_spec(const FamInfo& fi, const vb_target* tgt, const vb_objective* obj,
-                    const double* tparams, double tconst, const vbk::GlmHead& glm) {
+                    const double* tparams, double tconst, const TargetHeads& heads) {
   vbk::Spec f{};
   f.fam = fi;
   f.N = obj ? (int)obj->n_samples : 0;
@@ -722,7 +777,8 @@ vbk::Spec make_spec(const FamInfo& fi, const vb_target* tgt, const vb_objective*
   f.tparams = tparams;
   f.tconst = tconst;
   f.host = host_of(tgt);
-  f.glm = glm;
+  f.glm = heads.glm;
+  f.hier = heads.hier;
   return f;
 }
 
@@ -746,7 +802,7 @@ double sep_c0(const FamInfo& fi, bool pd) {
 // vb_objective_value_grad for the full-rank t family
 int fr_objective(vb_ctx* c, const FamInfo& fi, const vb_target* tgt, const vb_objective* obj,
                  const double* lam, const vb_noise* noise, double* value, double* grad,
-                 const vbk::GlmHead& glm) {
+                 const TargetHeads& heads) {
   const bool host = noise->kind == VB_NOISE_HOST;
   if (host && !noise->eps) return fail(VB_EINVAL, "host noise requires eps");
   const size_t N = (size_t)obj->n_samples;
@@ -757,7 +813,7 @@ int fr_objective(vb_ctx* c, const FamInfo& fi, const vb_target* tgt, const vb_ob
   VB_TRY(dg.stage(c, 2, grad, fi.P));
   const double* tp;
   double tc;
-  VB_TRY(target_params(c, tgt->kind == VB_TARGET_REGRESSION ? kSlotGlm : kSlotTparams, tgt, &tp,
+  VB_TRY(target_params(c, block_target(tgt->kind) ? kSlotGlm : kSlotTparams, tgt, &tp,
                        &tc));
   VB_TRY(c->slot[4].reserve(sizeof(double) * 2));
   vbk::FrWork* W;
@@ -765,7 +821,7 @@ int fr_objective(vb_ctx* c, const FamInfo& fi, const vb_target* tgt, const vb_ob
   // a root or gradient solve that needed more iterations than launched (an
   // ill-conditioned Sigma) runs the call again with larger counts (fr_info)
   for (int attempt = 0;; ++attempt) {
-    VB_TRY(vbk::fr_value_grad(W, make_spec(fi, tgt, obj, tp, tc, glm), dl.d,
+    VB_TRY(vbk::fr_value_grad(W, make_spec(fi, tgt, obj, tp, tc, heads), dl.d,
                               noise_of(noise, host ? dn.d : nullptr), c->slot[4].d(), dg.d,
                               c->stream));
     VB_TRY(sync(c));
@@ -998,8 +1054,8 @@ int vb_target_logdensity(vb_ctx* c, const vb_target* tgt, const double* x, int64
                          double* out, double* grad_out) {
   VB_TRY(check_ctx(c));
   if (!tgt) return fail(VB_EINVAL, "null target");
-  vbk::GlmHead glm{};
-  VB_TRY(check_target(tgt, (int)tgt->dim, &glm));
+  TargetHeads heads;
+  VB_TRY(check_target(tgt, (int)tgt->dim, &heads));
   if (!x || !out || n < 0) return fail(VB_EINVAL, "null argument");
   const int D = (int)tgt->dim;
   In dxx;
@@ -1019,7 +1075,13 @@ int vb_target_logdensity(vb_ctx* c, const vb_target* tgt, const double* x, int64
     VB_TRY(target_params(c, kSlotGlm, tgt, &tp, &tc));
     vbk::FrWork* W;
     VB_TRY(fr_work(c, &W));
-    VB_TRY(vbk::glm_target_eval(W, glm, D, n, tp, dxx.d, dout.d, dg.d, c->stream));
+    VB_TRY(vbk::glm_target_eval(W, heads.glm, D, n, tp, dxx.d, dout.d, dg.d, c->stream));
+  } else if (tgt->kind == VB_TARGET_HIERARCHICAL) {
+    if (n == 0) return VB_OK;
+    const double* tp;
+    double tc;
+    VB_TRY(target_params(c, kSlotGlm, tgt, &tp, &tc));
+    VB_HIP(vbk::launch_hier_rows(D, n, heads.hier, tp, dxx.d, dout.d, dg.d, c->stream));
   } else if (tgt->kind == VB_TARGET_CORR_GAUSS) {
     if (n == 0) return VB_OK;
     const double* tp;
@@ -1043,15 +1105,15 @@ int vb_objective_value_grad(vb_ctx* c, const vb_family* fam, const vb_target* tg
   VB_TRY(check_ctx(c));
   FamInfo fi;
   VB_TRY(check_family(fam, &fi));
-  vbk::GlmHead glm{};
-  VB_TRY(check_target(tgt, fi.D, &glm));
+  TargetHeads heads;
+  VB_TRY(check_target(tgt, fi.D, &heads));
   if (!obj || !lam || !noise || !value || !grad) return fail(VB_EINVAL, "null argument");
   VB_TRY(check_objective(obj));
   if (obj->kind == VB_OBJ_CHIVI && !(obj->alpha > 0))
     return fail(VB_EINVAL, "alpha must be positive");
   Path path;
   VB_TRY(choose_path({fi.kind, tgt->kind, fi.D, obj->kind}, &path));
-  if (path == Path::FullRank) return fr_objective(c, fi, tgt, obj, lam, noise, value, grad, glm);
+  if (path == Path::FullRank) return fr_objective(c, fi, tgt, obj, lam, noise, value, grad, heads);
   const int D = fi.D, N = (int)obj->n_samples;
   const size_t P = 2 * (size_t)D;
   const bool host = noise->kind == VB_NOISE_HOST;
@@ -1113,13 +1175,13 @@ int vb_objective_value_grad(vb_ctx* c, const vb_family* fam, const vb_target* tg
       break;
     }
     default: {
-      // CHIVI or a non-separable target at D > kBlockDMax, a callback or a regression block
+      // CHIVI or a non-separable target at D > kBlockDMax, a callback or a parameter block
       const double* tp;
       double tc;
       VB_TRY(target_params(c, kSlotGlm, tgt, &tp, &tc));
       vbk::FrWork* W;
       VB_TRY(fr_work(c, &W));
-      VB_TRY(vbk::mf_wide_value_grad(W, make_spec(fi, tgt, obj, tp, tc, glm), c->slot[3].d(), nz, dval,
+      VB_TRY(vbk::mf_wide_value_grad(W, make_spec(fi, tgt, obj, tp, tc, heads), c->slot[3].d(), nz, dval,
                                      dg.d, c->stream));
     }
   }
@@ -1192,8 +1254,8 @@ int vb_run_create(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const v
   *out = nullptr;
   FamInfo fi;
   VB_TRY(check_family(fam, &fi));
-  vbk::GlmHead glm{};
-  VB_TRY(check_target(tgt, fi.D, &glm));
+  TargetHeads heads;
+  VB_TRY(check_target(tgt, fi.D, &heads));
   VB_TRY(check_pairing(fi.kind, tgt->kind));  // reported before the argument errors below
   if (!obj || !cfg || !init) return fail(VB_EINVAL, "null argument");
   if (!(cfg->learning_rate > 0)) return fail(VB_EINVAL, "learning rate must be positive");
@@ -1244,7 +1306,7 @@ int vb_run_create(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const v
   // there (the caller's pointer is not kept)
   const double* run_tp = nullptr;
   double tc = 0.0;
-  if (fr || (wide && tgt->kind == VB_TARGET_REGRESSION)) {
+  if (fr || (wide && block_target(tgt->kind))) {
     const double* tp;
     if ((rc = target_params(c, kSlotRunTparams, tgt, &tp, &tc)) != VB_OK) return bail(rc);
     run_tp = tp;
@@ -1258,7 +1320,7 @@ int vb_run_create(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const v
     }
   }
   if (fr || wide) {
-    r->spec = make_spec(fi, tgt, obj, run_tp, tc, glm);
+    r->spec = make_spec(fi, tgt, obj, run_tp, tc, heads);
     if ((rc = r->grad.reserve(sizeof(double) * P)) != VB_OK) return bail(rc);
   }
   if ((rc = r->lam.reserve(sizeof(double) * P * n_problems)) != VB_OK) return bail(rc);
@@ -1823,8 +1885,8 @@ int vb_log_weights(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const 
   VB_TRY(check_ctx(c));
   FamInfo fi;
   VB_TRY(check_family(fam, &fi));
-  vbk::GlmHead glm{};
-  VB_TRY(check_target(tgt, fi.D, &glm));
+  TargetHeads heads;
+  VB_TRY(check_target(tgt, fi.D, &heads));
   if (!lam || !noise || !lw_out || m < 0) return fail(VB_EINVAL, "null argument");
   Path path;
   VB_TRY(choose_path({fi.kind, tgt->kind, fi.D}, &path));
@@ -1846,11 +1908,11 @@ int vb_log_weights(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const 
   } else {
     const double* tp;
     double tc;
-    const int slot = (!fr || tgt->kind == VB_TARGET_REGRESSION) ? kSlotGlm : kSlotTparamsLw;
+    const int slot = (!fr || block_target(tgt->kind)) ? kSlotGlm : kSlotTparamsLw;
     VB_TRY(target_params(c, slot, tgt, &tp, &tc));
     vbk::FrWork* W;
     VB_TRY(fr_work(c, &W));
-    const vbk::Spec f = make_spec(fi, tgt, nullptr, tp, tc, glm);
+    const vbk::Spec f = make_spec(fi, tgt, nullptr, tp, tc, heads);
     if (fr)
       VB_TRY(vbk::fr_log_weights(W, f, dl.d, m, nz, dlw.d, dxs.d, c->stream));
     else

@@ -1580,11 +1580,17 @@ int glm_target_eval(FrWork* W, const GlmHead& h, int D, long long n, const doubl
 }
 
 namespace {
-int eval_target(FrWork* W, int tgt, const HostTarget& host, const double* tparams,
-                const GlmHead& glm, int D, long long n, const double* x, double* logp,
+int eval_target(FrWork* W, const Spec& f, int D, long long n, const double* x, double* logp,
                 double* grad, hipStream_t st) {
-  if (tgt == kTargetCallback) return host_target_eval(W, host, D, n, x, logp, grad, st);
-  if (tgt == kTargetRegression) return glm_target_eval(W, glm, D, n, tparams, x, logp, grad, st);
+  const int tgt = f.tgt;
+  if (tgt == kTargetCallback) return host_target_eval(W, f.host, D, n, x, logp, grad, st);
+  if (tgt == kTargetRegression)
+    return glm_target_eval(W, f.glm, D, n, f.tparams, x, logp, grad, st);
+  if (tgt == kTargetHierarchical) {
+    if (!f.tparams) return vb_set_error(-1, "hierarchical target without parameters");
+    FR_HIP(launch_hier_rows(D, n, f.hier, f.tparams, x, logp, grad, st));
+    return 0;
+  }
   FR_HIP(launch_target_logdensity(tgt, D, n, x, logp, grad, st));
   return 0;
 }
@@ -2001,7 +2007,7 @@ int fr_value_grad(FrWork* W, const Spec& f, const double* lam, const Noise& nz, 
                          (f.chivi || f.pd) ? z : nullptr, W->X.d(), W->G.d(), f.tconst, 1,
                          W->zz.d(), W->logp.d());
   } else {
-    if (int rc = eval_target(W, f.tgt, f.host, f.tparams, f.glm, D, N, W->X.d(), W->logp.d(), W->G.d(), st)) return rc;
+    if (int rc = eval_target(W, f, D, N, W->X.d(), W->logp.d(), W->G.d(), st)) return rc;
     if (!fused && (f.chivi || f.pd))
       hipLaunchKernelGGL(fr_rows_kernel, dim3(blocks(N, 4)), dim3(256), 0, st, D, (long long)N,
                          z, nullptr, nullptr, 0.0, 0, W->zz.d(), nullptr);
@@ -2119,7 +2125,7 @@ int fr_log_weights(FrWork* W, const Spec& f, const double* lam, long long m, con
     hipLaunchKernelGGL(fr_rows_kernel, dim3(blocks(m, 4)), dim3(256), 0, st, D, m, z, x, W->G.d(),
                        f.tconst, 1, W->zz.d(), W->logp.d());
   } else {
-    if (int rc = eval_target(W, f.tgt, f.host, f.tparams, f.glm, D, m, x, W->logp.d(), nullptr, st)) return rc;
+    if (int rc = eval_target(W, f, D, m, x, W->logp.d(), nullptr, st)) return rc;
     hipLaunchKernelGGL(fr_rows_kernel, dim3(blocks(m, 4)), dim3(256), 0, st, D, m, z, nullptr,
                        nullptr, 0.0, 0, W->zz.d(), nullptr);
   }
@@ -2387,7 +2393,7 @@ int mf_wide_value_grad(FrWork* W, const Spec& f, const double* lam, const Noise&
                            st));
   } else {
     FR_HIP(launch_sample(f.fam, N, lam, nz, W->X.d(), st));
-    if (int rc = eval_target(W, f.tgt, f.host, f.tparams, f.glm, D, N, W->X.d(), W->logp.d(), W->G.d(), st))
+    if (int rc = eval_target(W, f, D, N, W->X.d(), W->logp.d(), W->G.d(), st))
       return rc;
     if (f.chivi || f.pd)
       FR_HIP(launch_family_logdensity(f.fam, N, lam, W->X.d(), W->zz.d(), st));
@@ -2454,7 +2460,7 @@ int mf_wide_log_weights(FrWork* W, const Spec& f, const double* lam, long long m
   } else {
     FR_HIP(launch_sample(f.fam, m, lam, nz, x, st));
   }
-  if (int rc = eval_target(W, f.tgt, f.host, f.tparams, f.glm, D, m, x, W->logp.d(), nullptr, st)) return rc;
+  if (int rc = eval_target(W, f, D, m, x, W->logp.d(), nullptr, st)) return rc;
   FR_HIP(launch_family_logdensity(f.fam, m, lam, x, W->zz.d(), st));
   hipLaunchKernelGGL(sub_kernel, dim3(blocks(m)), dim3(256), 0, st, m, W->logp.d(), W->zz.d(), lw);
   FR_HIP(hipGetLastError());

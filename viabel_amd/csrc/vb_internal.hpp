@@ -228,6 +228,22 @@ size_t glm_scratch_doubles(int D, long long n, long long M, bool grad);
 hipError_t launch_glm_rows(int D, long long n, const GlmHead& h, const double* params,
                            const double* x, double* logp, double* grad, double* scratch,
                            hipStream_t s);
+constexpr int kTargetHierarchical = 7;
+// Hierarchical normal means (vb_hier.hip): host copy of the parameter block's header
+// (include/viabel_amd.h); y [J] starts kHierHeader doubles into the block, sigma [J]
+// follows it.
+constexpr int kHierHeader = 8;
+struct HierHead {
+  int centered;       // 0 non-centred, 1 centred
+  long long J;        // groups; D = J + 2
+  double mu_scale, tau_scale;
+};
+// log p [n] and (grad non-null) d log p / dx [n][D] of the rows of x [n][D] for the
+// hierarchical target whose parameter block is at `params` (device).  grad == nullptr
+// selects instances without any gradient operation or store.  No atomics and no
+// scratch; a row's bits do not depend on n.
+hipError_t launch_hier_rows(int D, long long n, const HierHead& h, const double* params,
+                            const double* x, double* logp, double* grad, hipStream_t s);
 // host model callback (vb_target_callback) + its user pointer
 struct HostTarget {
   int (*fn)(void* user, const double* x, int64_t n, int64_t d, double* logp, double* grad);
@@ -250,10 +266,11 @@ struct Spec {
   Family fam;
   int N, tgt, chivi, pd;
   double alpha;
-  const double* tparams;  // device; corr_gauss: P*[D][D]; regression: the parameter block
+  const double* tparams;  // device; corr_gauss: P*[D][D]; regression / hierarchical: the block
   double tconst;          // corr_gauss log normaliser
   HostTarget host;        // tgt == kTargetCallback
   GlmHead glm;            // tgt == kTargetRegression
+  HierHead hier;          // tgt == kTargetHierarchical
 };
 
 // All return 0 or a VB_E* code (message via vb_set_error).

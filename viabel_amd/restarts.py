@@ -78,7 +78,7 @@ def _rows_supported(fam, target):
     from .targets import Target
     if fam.kind == nat.FAMILY_FR_T or not isinstance(target, Target):
         return False
-    if target.kind in (nat.TARGET_CALLBACK, nat.TARGET_REGRESSION):
+    if target.kind in (nat.TARGET_CALLBACK, nat.TARGET_REGRESSION, nat.TARGET_HIERARCHICAL):
         return False
     return target.separable or fam.dim <= _ROWS_DMAX
 

@@ -20,6 +20,12 @@ Targets:
                          (robust-regression.ipynb; VB_TARGET_REGRESSION)
   robust_regression(x, y, df)   regression with the student_t likelihood
   logistic_regression(x, y)     regression with the bernoulli_logit likelihood
+  hierarchical_normal(y, sigma, centered=False, ...)
+                         hierarchical normal means over J groups held on the device,
+                         x = [mu, log tau, theta or theta_tilde (J)], D = J + 2, centred
+                         or non-centred (VB_TARGET_HIERARCHICAL)
+  eight_schools_cp()     eight_schools_cp.stan log_prob (D = 10): hierarchical_normal
+                         with the eight-schools data, centred       eight-schools.ipynb
 
 User models (the reference's make_stan_log_density, vb.py:314-321, and autograd
 callables): callback(fn, D), from_stan(fit, D) and torch_target(f, D) evaluate
@@ -34,6 +40,7 @@ from . import _native as nat
 
 __all__ = ['Target', 'isogauss', 'mixture', 'funnel', 'eight_schools_ncp', 'corr_gauss',
            'regression', 'robust_regression', 'logistic_regression',
+           'hierarchical_normal', 'eight_schools_cp',
            'callback', 'from_stan', 'torch_target', 'as_target']
 
 
@@ -177,6 +184,55 @@ def robust_regression(x, y, df, scale=1.0, prior_scale=10.0):
 def logistic_regression(x, y, prior_scale=10.0):
     """y ~ bernoulli_logit(x beta), beta ~ normal(0, prior_scale)."""
     return regression(x, y, 'bernoulli_logit', prior_scale=prior_scale)
+
+
+HIERARCHICAL_HEADER = 8   # doubles before y in a hierarchical target's parameter block
+EIGHT_SCHOOLS_Y = (28., 8., -3., 7., -1., 1., 18., 12.)
+EIGHT_SCHOOLS_SIGMA = (15., 10., 16., 11., 9., 11., 10., 18.)
+
+
+def hierarchical_normal(y, sigma, centered=False, mu_scale=5.0, tau_scale=5.0):
+    """Hierarchical normal means evaluated on the device: J groups with estimates
+    y_j and standard errors sigma_j,
+      mu ~ N(0, mu_scale^2), tau ~ half-Cauchy(0, tau_scale), y_j ~ N(theta_j, sigma_j^2)
+      centred       theta_j ~ N(mu, tau^2),          x = [mu, log tau, theta (J)]
+      non-centred   theta_j = mu + tau theta_tilde_j, theta_tilde_j ~ N(0, 1),
+                                                     x = [mu, log tau, theta_tilde (J)]
+    in Stan's log_prob convention (constants of the ~ statements dropped, the
+    Jacobian of tau = exp(log tau) kept), so D = J + 2.  The data are packed once
+    into one parameter array (layout in include/viabel_amd.h) that the library
+    uploads per run, so no host call happens inside a fit."""
+    y = np.asarray(y, dtype=np.float64)
+    sigma = np.asarray(sigma, dtype=np.float64)
+    if y.ndim != 1 or y.shape[0] < 1:
+        raise ValueError('y must be a non-empty 1-D array, got shape %s' % (y.shape,))
+    if sigma.shape != y.shape:
+        raise ValueError('sigma must have shape %s, got %s' % (y.shape, sigma.shape))
+    if not (np.all(np.isfinite(y)) and np.all(np.isfinite(sigma))):
+        raise ValueError('y and sigma must be finite')
+    if not np.all(sigma > 0):
+        raise ValueError('sigma must be positive')
+    if not (np.isfinite(mu_scale) and mu_scale > 0):
+        raise ValueError('mu_scale must be positive')
+    if not (np.isfinite(tau_scale) and tau_scale > 0):
+        raise ValueError('tau_scale must be positive')
+    j = y.shape[0]
+    params = np.zeros(HIERARCHICAL_HEADER + 2 * j)
+    params[0] = 1.0 if centered else 0.0
+    params[1] = j
+    params[2] = mu_scale
+    params[3] = tau_scale
+    params[HIERARCHICAL_HEADER:HIERARCHICAL_HEADER + j] = y
+    params[HIERARCHICAL_HEADER + j:] = sigma
+    t = Target(nat.TARGET_HIERARCHICAL, j + 2, 'hierarchical_normal', params)
+    t.n_groups = j
+    t.centered = bool(centered)
+    return t
+
+
+def eight_schools_cp():
+    """eight_schools_cp.stan: the centred eight-schools model (D = 10)."""
+    return hierarchical_normal(EIGHT_SCHOOLS_Y, EIGHT_SCHOOLS_SIGMA, centered=True)
 
 
 def callback(logdensity_and_grad, dim=None, name='callback'):
