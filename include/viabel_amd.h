@@ -89,8 +89,11 @@ enum vb_target_kind {
                                  batch of samples; everything else stays on the device */
   VB_TARGET_REGRESSION = 6,   /* generalised linear model over a data matrix in `params`
                                  (layout below), evaluated on the device; any family, any D */
-  VB_TARGET_HIERARCHICAL = 7  /* hierarchical normal means over J groups in `params` (layout
+  VB_TARGET_HIERARCHICAL = 7, /* hierarchical normal means over J groups in `params` (layout
                                  below), centred or non-centred; any family, D = J + 2 */
+  VB_TARGET_MULTILEVEL = 8    /* regression with group intercepts sharing a learned scale, data
+                                 and group offsets in `params` (layout below), centred or
+                                 non-centred; any family, D = p + 1 + G */
 };
 
 /* VB_TARGET_REGRESSION: log p(beta) = sum_d log N(beta_d; 0, s^2) + sum_m l(y_m, eta_m),
@@ -128,6 +131,32 @@ enum vb_target_kind {
  *   n_params = 8 + 2 J
  * With the eight-schools data and s_mu = s_tau = 5 the non-centred form is
  * VB_TARGET_EIGHT_SCHOOLS_NCP's density.  Staged and copied as the regression block is. */
+
+/* VB_TARGET_MULTILEVEL: a regression whose intercept varies by group.  M observations
+ * sorted by group, p >= 1 fixed effects, G groups; unconstrained
+ * x = [beta (p), u = log tau, then G more], dim = p + 1 + G; the normalised joint density
+ * in these coordinates (every constant and the Jacobian term +u kept), tau = exp(u):
+ *   beta_d ~ N(0, s^2), tau ~ half-Cauchy(0, s_tau)
+ *   centred      a_g ~ N(0, tau^2), the coordinate is a_g
+ *   non-centred  a_g = tau at_g, at_g ~ N(0, 1), the coordinate is at_g
+ *   eta_m = x_m . beta + a_g(m); y_m | eta_m through the likelihoods of
+ *   VB_TARGET_REGRESSION
+ * vb_target.params (host or device memory):
+ *   params[0] likelihood: 0 gaussian, 1 student_t, 2 bernoulli_logit
+ *   params[1] M (number of observations, >= 1, integral)
+ *   params[2] nu   (student_t degrees of freedom, > 0; ignored otherwise)
+ *   params[3] sigma (gaussian / student_t scale, > 0; ignored for bernoulli_logit)
+ *   params[4] prior_scale s (> 0)
+ *   params[5] G (number of groups, >= 1, integral)
+ *   params[6] s_tau (> 0)
+ *   params[7] form: 0 non-centred, 1 centred
+ *   params[8 ..]                X, row-major [M][p]
+ *   params[8 + M*p ..]          y [M]   (bernoulli_logit: 0 or 1)
+ *   params[8 + M*p + M ..]      off [G + 1]: group g holds the observations
+ *                               off[g] <= m < off[g + 1]; exact integers, off[0] = 0,
+ *                               off[G] = M, non-decreasing (an empty group has its prior only)
+ *   n_params = 8 + M*p + M + G + 1
+ * Staged and copied as the regression block is. */
 
 /* User target: log p and d log p / dx of the n rows of x [n][d] (HOST memory,
  * C order) into logp [n] and grad [n][d]; return 0, or non-zero to abort the

@@ -21,6 +21,7 @@ TARGET_CORR_GAUSS = 4
 TARGET_CALLBACK = 5
 TARGET_REGRESSION = 6
 TARGET_HIERARCHICAL = 7
+TARGET_MULTILEVEL = 8
 OBJ_KLVI, OBJ_CHIVI, OBJ_KLVI_PD = 0, 1, 2
 OPT_ADAGRAD, OPT_RMSPROP_IA, OPT_ADAM_IA, OPT_RMSPROP_IA_NORM = 0, 1, 2, 3
 NOISE_HOST, NOISE_PHILOX = 0, 1

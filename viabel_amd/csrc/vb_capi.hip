@@ -628,20 +628,92 @@ int hierarchical_head(const vb_target* t, vbk::HierHead* o) {
   return VB_OK;
 }
 
+// Header and group offsets of a multilevel target's parameter block
+// (include/viabel_amd.h), read from host or device memory and checked against n_params
+// and dim.
+int multilevel_head(const vb_target* t, vbk::MlmHead* o) {
+  if (!t->params || t->n_params < vbk::kMlmHeader)
+    return fail(VB_EINVAL, "multilevel target: n_params %lld is shorter than the %d-value header",
+                (long long)t->n_params, vbk::kMlmHeader);
+  double h[vbk::kMlmHeader];
+  const int pc = ptr_class(t->params);
+  if (pc < 0) return foreign_ptr_error(t->params);
+  if (pc == 1)
+    VB_HIP(hipMemcpy(h, t->params, sizeof h, hipMemcpyDeviceToHost));
+  else
+    std::memcpy(h, t->params, sizeof h);
+  if (!(h[0] == 0.0 || h[0] == 1.0 || h[0] == 2.0))
+    return fail(VB_EINVAL, "multilevel target: params[0] (likelihood) must be 0, 1 or 2, got %g", h[0]);
+  if (!(h[1] >= 1.0 && h[1] <= 9.0e15 && h[1] == std::floor(h[1])))
+    return fail(VB_EINVAL, "multilevel target: params[1] (M) must be an integer >= 1, got %g", h[1]);
+  const int lik = (int)h[0];
+  if (lik == 1 && !(h[2] > 0.0 && std::isfinite(h[2])))
+    return fail(VB_EINVAL, "multilevel target: params[2] (nu) must be positive, got %g", h[2]);
+  if (lik != 2 && !(h[3] > 0.0 && std::isfinite(h[3])))
+    return fail(VB_EINVAL, "multilevel target: params[3] (sigma) must be positive, got %g", h[3]);
+  if (!(h[4] > 0.0 && std::isfinite(h[4])))
+    return fail(VB_EINVAL, "multilevel target: params[4] (prior_scale) must be positive, got %g", h[4]);
+  if (!(h[5] >= 1.0 && h[5] <= 2.0e9 && h[5] == std::floor(h[5])))
+    return fail(VB_EINVAL, "multilevel target: params[5] (G) must be an integer >= 1, got %g", h[5]);
+  if (!(h[6] > 0.0 && std::isfinite(h[6])))
+    return fail(VB_EINVAL, "multilevel target: params[6] (tau_scale) must be positive, got %g", h[6]);
+  if (!(h[7] == 0.0 || h[7] == 1.0))
+    return fail(VB_EINVAL, "multilevel target: params[7] (form) must be 0 or 1, got %g", h[7]);
+  const double p = (double)t->dim - 1.0 - h[5];
+  if (!(p >= 1.0))
+    return fail(VB_EINVAL, "multilevel target: dim %lld does not leave p >= 1 beside 1 + G = %.0f",
+                (long long)t->dim, 1.0 + h[5]);
+  const double want = (double)vbk::kMlmHeader + h[1] * p + h[1] + h[5] + 1.0;
+  if ((double)t->n_params != want)
+    return fail(VB_EINVAL,
+                "multilevel target: n_params %lld does not match 8 + M*p + M + G + 1 = %.0f (M %.0f, "
+                "p %.0f, G %.0f)", (long long)t->n_params, want, h[1], p, h[5]);
+  // the group offsets: exact integers, 0 first, M last, non-decreasing
+  const size_t ng = (size_t)h[5] + 1;
+  const double* offp = t->params + (size_t)(want - (double)ng);
+  std::vector<double> off(ng);
+  if (pc == 1)
+    VB_HIP(hipMemcpy(off.data(), offp, sizeof(double) * ng, hipMemcpyDeviceToHost));
+  else
+    std::memcpy(off.data(), offp, sizeof(double) * ng);
+  if (off[0] != 0.0)
+    return fail(VB_EINVAL, "multilevel target: the first group offset must be 0, got %g", off[0]);
+  if (off[ng - 1] != h[1])
+    return fail(VB_EINVAL, "multilevel target: the last group offset must be M = %.0f, got %g", h[1],
+                off[ng - 1]);
+  for (size_t g = 1; g < ng; ++g)
+    if (!(off[g] >= off[g - 1] && off[g] == std::floor(off[g])))
+      return fail(VB_EINVAL,
+                  "multilevel target: group offsets must be non-decreasing integers, got %g after %g "
+                  "at group %lld", off[g], off[g - 1], (long long)g);
+  o->lik = lik;
+  o->centered = (int)h[7];
+  o->M = (long long)h[1];
+  o->G = (long long)h[5];
+  o->nu = h[2];
+  o->sigma = h[3];
+  o->prior = h[4];
+  o->tau_scale = h[6];
+  return VB_OK;
+}
+
 // Host copies of the headers of the targets that carry a parameter block.
 struct TargetHeads {
   vbk::GlmHead glm{};
   vbk::HierHead hier{};
+  vbk::MlmHead mlm{};
 };
 
-// Whether the target's `params` is a block used whole (regression, hierarchical).
+// Whether the target's `params` is a block used whole (regression, hierarchical,
+// multilevel).
 bool block_target(int kind) {
-  return kind == VB_TARGET_REGRESSION || kind == VB_TARGET_HIERARCHICAL;
+  return kind == VB_TARGET_REGRESSION || kind == VB_TARGET_HIERARCHICAL ||
+         kind == VB_TARGET_MULTILEVEL;
 }
 
 int check_target(const vb_target* t, int D, TargetHeads* heads = nullptr) {
   if (!t) return fail(VB_EINVAL, "null vb_target");
-  if (t->kind < VB_TARGET_ISOGAUSS || t->kind > VB_TARGET_HIERARCHICAL)
+  if (t->kind < VB_TARGET_ISOGAUSS || t->kind > VB_TARGET_MULTILEVEL)
     return fail(VB_EUNSUPPORTED, "target kind %d is not implemented on the device", t->kind);
   if (t->kind == VB_TARGET_CALLBACK && !t->callback)
     return fail(VB_EINVAL, "callback target needs a callback");
@@ -663,6 +735,11 @@ int check_target(const vb_target* t, int D, TargetHeads* heads = nullptr) {
     vbk::HierHead h{};
     VB_TRY(hierarchical_head(t, &h));
     if (heads) heads->hier = h;
+  }
+  if (t->kind == VB_TARGET_MULTILEVEL) {
+    vbk::MlmHead h{};
+    VB_TRY(multilevel_head(t, &h));
+    if (heads) heads->mlm = h;
   }
   return VB_OK;
 }
@@ -779,6 +856,7 @@ vbk::Spec make_spec(const FamInfo& fi, const vb_target* tgt, const vb_objective*
   f.host = host_of(tgt);
   f.glm = heads.glm;
   f.hier = heads.hier;
+  f.mlm = heads.mlm;
   return f;
 }
 
@@ -1082,6 +1160,14 @@ int vb_target_logdensity(vb_ctx* c, const vb_target* tgt, const double* x, int64
     double tc;
     VB_TRY(target_params(c, kSlotGlm, tgt, &tp, &tc));
     VB_HIP(vbk::launch_hier_rows(D, n, heads.hier, tp, dxx.d, dout.d, dg.d, c->stream));
+  } else if (tgt->kind == VB_TARGET_MULTILEVEL) {
+    if (n == 0) return VB_OK;
+    const double* tp;
+    double tc;
+    VB_TRY(target_params(c, kSlotGlm, tgt, &tp, &tc));
+    vbk::FrWork* W;
+    VB_TRY(fr_work(c, &W));
+    VB_TRY(vbk::mlm_target_eval(W, heads.mlm, D, n, tp, dxx.d, dout.d, dg.d, c->stream));
   } else if (tgt->kind == VB_TARGET_CORR_GAUSS) {
     if (n == 0) return VB_OK;
     const double* tp;

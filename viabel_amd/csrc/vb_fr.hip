@@ -1450,7 +1450,7 @@ struct FrWork {
   } wsnap_h{};
   // N x D / N
   Buf Z, X, G, s, logp, zz, r, rk;
-  Buf glm;  // regression target: chunk partials (glm_target_eval)
+  Buf glm;  // regression / multilevel target: chunk partials (glm_target_eval, mlm_target_eval)
   // pinned host staging for host-callback targets
   double *hx = nullptr, *hlp = nullptr, *hg = nullptr;
   size_t hcap = 0;
@@ -1579,6 +1579,14 @@ int glm_target_eval(FrWork* W, const GlmHead& h, int D, long long n, const doubl
   return 0;
 }
 
+int mlm_target_eval(FrWork* W, const MlmHead& h, int D, long long n, const double* tparams,
+                    const double* x, double* logp, double* grad, hipStream_t st) {
+  if (!tparams) return vb_set_error(-1, "multilevel target without parameters");
+  FR_HIP(W->glm.reserve(sizeof(double) * mlm_scratch_doubles(D, n, h, grad != nullptr)));
+  FR_HIP(launch_mlm_rows(D, n, h, tparams, x, logp, grad, W->glm.d(), st));
+  return 0;
+}
+
 namespace {
 int eval_target(FrWork* W, const Spec& f, int D, long long n, const double* x, double* logp,
                 double* grad, hipStream_t st) {
@@ -1591,6 +1599,8 @@ int eval_target(FrWork* W, const Spec& f, int D, long long n, const double* x, d
     FR_HIP(launch_hier_rows(D, n, f.hier, f.tparams, x, logp, grad, st));
     return 0;
   }
+  if (tgt == kTargetMultilevel)
+    return mlm_target_eval(W, f.mlm, D, n, f.tparams, x, logp, grad, st);
   FR_HIP(launch_target_logdensity(tgt, D, n, x, logp, grad, st));
   return 0;
 }

@@ -244,6 +244,26 @@ struct HierHead {
 // scratch; a row's bits do not depend on n.
 hipError_t launch_hier_rows(int D, long long n, const HierHead& h, const double* params,
                             const double* x, double* logp, double* grad, hipStream_t s);
+constexpr int kTargetMultilevel = 8;
+// Multilevel regression (vb_mlm.hip): host copy of the parameter block's header
+// (include/viabel_amd.h); X [M][p] starts kMlmHeader doubles into the block, y [M] and
+// the G + 1 group offsets follow it.
+constexpr int kMlmHeader = 8;
+struct MlmHead {
+  int lik;            // 0 gaussian, 1 student_t, 2 bernoulli_logit
+  int centered;       // 0 non-centred, 1 centred
+  long long M, G;     // observations, groups; D = p + 1 + G
+  double nu, sigma, prior, tau_scale;
+};
+// log p [n] and (grad non-null) d log p / dx [n][D] of the rows of x [n][D] for the
+// multilevel target whose parameter block is at `params` (device).  scratch holds
+// mlm_scratch_doubles(D, n, h, grad != null) doubles of chunk partials.  grad == nullptr
+// selects instances without gradient work; their values equal the with-gradient
+// values bit for bit.  No atomics; two identical calls give identical bits.
+size_t mlm_scratch_doubles(int D, long long n, const MlmHead& h, bool grad);
+hipError_t launch_mlm_rows(int D, long long n, const MlmHead& h, const double* params,
+                           const double* x, double* logp, double* grad, double* scratch,
+                           hipStream_t s);
 // host model callback (vb_target_callback) + its user pointer
 struct HostTarget {
   int (*fn)(void* user, const double* x, int64_t n, int64_t d, double* logp, double* grad);
@@ -266,11 +286,13 @@ struct Spec {
   Family fam;
   int N, tgt, chivi, pd;
   double alpha;
-  const double* tparams;  // device; corr_gauss: P*[D][D]; regression / hierarchical: the block
+  const double* tparams;  // device; corr_gauss: P*[D][D]; regression / hierarchical /
+                          // multilevel: the block
   double tconst;          // corr_gauss log normaliser
   HostTarget host;        // tgt == kTargetCallback
   GlmHead glm;            // tgt == kTargetRegression
   HierHead hier;          // tgt == kTargetHierarchical
+  MlmHead mlm;            // tgt == kTargetMultilevel
 };
 
 // All return 0 or a VB_E* code (message via vb_set_error).
@@ -289,6 +311,9 @@ int fr_target(FrWork* W, int tgt, int D, long long n, const double* tparams, dou
               const double* x, double* logp, double* G, hipStream_t st);
 // regression target at device x [n][D] (grad nullable); chunk partials in the workspace
 int glm_target_eval(FrWork* W, const GlmHead& h, int D, long long n, const double* tparams,
+                    const double* x, double* logp, double* grad, hipStream_t st);
+// multilevel target at device x [n][D] (grad nullable); chunk partials in the workspace
+int mlm_target_eval(FrWork* W, const MlmHead& h, int D, long long n, const double* tparams,
                     const double* x, double* logp, double* grad, hipStream_t st);
 struct MfUpdate;
 // The next step of a fused run: its draws (rng step `step`) and L are prepared by

@@ -78,7 +78,8 @@ def _rows_supported(fam, target):
     from .targets import Target
     if fam.kind == nat.FAMILY_FR_T or not isinstance(target, Target):
         return False
-    if target.kind in (nat.TARGET_CALLBACK, nat.TARGET_REGRESSION, nat.TARGET_HIERARCHICAL):
+    if target.kind in (nat.TARGET_CALLBACK, nat.TARGET_REGRESSION, nat.TARGET_HIERARCHICAL,
+                       nat.TARGET_MULTILEVEL):
         return False
     return target.separable or fam.dim <= _ROWS_DMAX
 

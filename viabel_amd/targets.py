@@ -26,6 +26,13 @@ Targets:
                          or non-centred (VB_TARGET_HIERARCHICAL)
   eight_schools_cp()     eight_schools_cp.stan log_prob (D = 10): hierarchical_normal
                          with the eight-schools data, centred       eight-schools.ipynb
+  multilevel_regression(x, y, group, likelihood='gaussian', centered=False, ...)
+                         regression with group intercepts a_g sharing a learned scale tau,
+                         held on the device: x = [beta (p), log tau, a or a_tilde (G)],
+                         D = p + 1 + G, the three likelihoods of regression, centred or
+                         non-centred (VB_TARGET_MULTILEVEL)
+  multilevel_logistic_regression(x, y, group)     ... with the bernoulli_logit likelihood
+  multilevel_robust_regression(x, y, group, df)   ... with the student_t likelihood
 
 User models (the reference's make_stan_log_density, vb.py:314-321, and autograd
 callables): callback(fn, D), from_stan(fit, D) and torch_target(f, D) evaluate
@@ -41,6 +48,8 @@ from . import _native as nat
 __all__ = ['Target', 'isogauss', 'mixture', 'funnel', 'eight_schools_ncp', 'corr_gauss',
            'regression', 'robust_regression', 'logistic_regression',
            'hierarchical_normal', 'eight_schools_cp',
+           'multilevel_regression', 'multilevel_logistic_regression',
+           'multilevel_robust_regression',
            'callback', 'from_stan', 'torch_target', 'as_target']
 
 
@@ -233,6 +242,107 @@ def hierarchical_normal(y, sigma, centered=False, mu_scale=5.0, tau_scale=5.0):
 def eight_schools_cp():
     """eight_schools_cp.stan: the centred eight-schools model (D = 10)."""
     return hierarchical_normal(EIGHT_SCHOOLS_Y, EIGHT_SCHOOLS_SIGMA, centered=True)
+
+
+MULTILEVEL_HEADER = 8   # doubles before X in a multilevel target's parameter block
+
+
+def multilevel_regression(x, y, group, likelihood='gaussian', df=None, scale=1.0,
+                          prior_scale=10.0, tau_scale=5.0, centered=False, n_groups=None):
+    """A regression whose intercept varies by group, evaluated on the device:
+      beta_d ~ N(0, prior_scale^2), tau ~ half-Cauchy(0, tau_scale)
+      centred       a_g ~ N(0, tau^2),               x = [beta (p), log tau, a (G)]
+      non-centred   a_g = tau a_tilde_g, a_tilde_g ~ N(0, 1),
+                                                     x = [beta (p), log tau, a_tilde (G)]
+      eta_m = x_m . beta + a_group[m], y_m | eta_m as in `regression`
+    with every normalising constant and the Jacobian of tau = exp(log tau) kept, so
+    D = p + 1 + G.  x is (M, p), y is (M,), group is (M,) integer labels in 0 .. G - 1
+    with G = n_groups, or max(group) + 1; a group without observations has its prior
+    only.  The observations are sorted by group once (a stable sort, the permutation
+    kept as `order`) and packed with the group offsets into one parameter array
+    (layout in include/viabel_amd.h) that the library uploads per run, so no host call
+    happens inside a fit."""
+    if likelihood not in _LIKELIHOODS:
+        raise ValueError('unknown likelihood %r (expected one of %s)'
+                         % (likelihood, ', '.join(sorted(_LIKELIHOODS))))
+    x = np.asarray(x, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    if x.ndim != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError('x must be a non-empty (M, p) matrix, got shape %s' % (x.shape,))
+    m, p = x.shape
+    if y.shape != (m,):
+        raise ValueError('y must have shape (%d,), got %s' % (m, y.shape))
+    graw = np.asarray(group)
+    if graw.shape != (m,):
+        raise ValueError('group must have shape (%d,), got %s' % (m, graw.shape))
+    if graw.dtype.kind not in 'iuf':
+        raise ValueError('group must hold integer labels, got dtype %s' % graw.dtype)
+    if graw.dtype.kind == 'f' and not (np.all(np.isfinite(graw)) and np.all(graw == np.floor(graw))):
+        raise ValueError('group must hold integer labels')
+    if np.any(graw < 0):
+        raise ValueError('group labels must be >= 0')
+    if np.any(graw >= 2 ** 31):
+        raise ValueError('group labels must be below 2^31')
+    g = graw.astype(np.int64)
+    if n_groups is None:
+        n_groups = int(g.max()) + 1
+    elif not (isinstance(n_groups, (int, np.integer)) and n_groups >= 1):
+        raise ValueError('n_groups must be an integer >= 1')
+    n_groups = int(n_groups)
+    if int(g.max()) >= n_groups:
+        raise ValueError('group label %d is not below n_groups = %d' % (int(g.max()), n_groups))
+    if not (np.all(np.isfinite(x)) and np.all(np.isfinite(y))):
+        raise ValueError('x and y must be finite')
+    if not (np.isfinite(prior_scale) and prior_scale > 0):
+        raise ValueError('prior_scale must be positive')
+    if not (np.isfinite(tau_scale) and tau_scale > 0):
+        raise ValueError('tau_scale must be positive')
+    if likelihood == 'student_t':
+        if df is None or not (np.isfinite(df) and df > 0):
+            raise ValueError('the student_t likelihood needs df > 0')
+    if likelihood != 'bernoulli_logit':
+        if not (np.isfinite(scale) and scale > 0):
+            raise ValueError('scale must be positive')
+    elif not np.all((y == 0) | (y == 1)):
+        raise ValueError('the bernoulli_logit likelihood needs y in {0, 1}')
+    order = np.argsort(g, kind='stable')
+    offsets = np.concatenate([[0], np.cumsum(np.bincount(g, minlength=n_groups))])
+    h = MULTILEVEL_HEADER
+    params = np.zeros(h + m * p + m + n_groups + 1)
+    params[0] = _LIKELIHOODS[likelihood]
+    params[1] = m
+    params[2] = df if likelihood == 'student_t' else 0.0
+    params[3] = scale if likelihood != 'bernoulli_logit' else 0.0
+    params[4] = prior_scale
+    params[5] = n_groups
+    params[6] = tau_scale
+    params[7] = 1.0 if centered else 0.0
+    params[h:h + m * p] = x[order].ravel()
+    params[h + m * p:h + m * p + m] = y[order]
+    params[h + m * p + m:] = offsets
+    t = Target(nat.TARGET_MULTILEVEL, p + 1 + n_groups, 'multilevel_regression', params)
+    t.likelihood = likelihood
+    t.n_obs = m
+    t.n_groups = n_groups
+    t.centered = bool(centered)
+    t.order = order
+    return t
+
+
+def multilevel_logistic_regression(x, y, group, prior_scale=10.0, tau_scale=5.0, centered=False,
+                                   n_groups=None):
+    """Random-intercept logistic regression: multilevel_regression with the
+    bernoulli_logit likelihood."""
+    return multilevel_regression(x, y, group, 'bernoulli_logit', prior_scale=prior_scale,
+                                 tau_scale=tau_scale, centered=centered, n_groups=n_groups)
+
+
+def multilevel_robust_regression(x, y, group, df, scale=1.0, prior_scale=10.0, tau_scale=5.0,
+                                 centered=False, n_groups=None):
+    """multilevel_regression with the student_t likelihood."""
+    return multilevel_regression(x, y, group, 'student_t', df=df, scale=scale,
+                                 prior_scale=prior_scale, tau_scale=tau_scale, centered=centered,
+                                 n_groups=n_groups)
 
 
 def callback(logdensity_and_grad, dim=None, name='callback'):
