@@ -32,6 +32,31 @@ def divergence_bound(lw, alpha=2., log_norm_bound=None, return_log_norm_bound=Fa
     return (d, log_norm_bound) if return_log_norm_bound else d
 
 
+def divergence_stats(lw, alpha=2., log_norm_bound=None):
+    """The seven values divergence_bound passes through (bounds.py:142-192), by the
+    same numpy expressions and without the warnings: d_alpha, log_norm_bound,
+    mean_r, se_r, mean_lw, se_lw, max."""
+    lw = np.asarray(lw)
+    with np.errstate(all='ignore'):
+        top = np.max(lw)
+        r = np.exp(lw - top) ** alpha
+        mean_r, se_r = np.mean(r), np.std(r) / np.sqrt(r.size)
+        mean_lw, se_lw = np.mean(lw), np.std(lw) / np.sqrt(lw.size)
+        cubo = np.log(mean_r) / alpha + top
+        lnb = mean_lw if log_norm_bound is None else log_norm_bound
+        d = alpha / (alpha - 1) * (cubo - lnb)
+    return np.array([d, lnb, mean_r, se_r, mean_lw, se_lw, top])
+
+
+def centered_moments(samples):
+    """bounds.py:133-135: (C2, C4), the mean over rows of sum_d (x - mean)^p."""
+    xs = np.asarray(samples)
+    if xs.ndim == 1:
+        xs = xs[:, None]
+    xc = xs - xs.mean(axis=0, keepdims=True)
+    return np.mean(np.sum(xc ** 2, axis=1)), np.mean(np.sum(xc ** 4, axis=1))
+
+
 def wasserstein_bounds(d2, samples=None, moment_bound_fn=None):
     """bounds.py:103-139."""
     if moment_bound_fn is None:

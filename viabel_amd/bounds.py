@@ -142,6 +142,19 @@ def divergence_bound(log_weights, alpha=2., log_norm_bound=None,
     return dalpha
 
 
+def _device_rows(a):
+    """`a` if it is a float64 device tensor whose rows are contiguous, at any leading
+    dimension >= the row length (a column slice t[:, :n] is read in place); any other
+    device tensor goes through nat.device_tensor's check, which refuses what is not
+    contiguous (a transposed tensor, a row slice with a step: TypeError, as before);
+    None for host data."""
+    if getattr(a, 'is_cuda', False) and hasattr(a, 'data_ptr') and a.dim() == 2:
+        import torch
+        if a.dtype == torch.float64 and a.stride(1) == 1 and a.stride(0) >= a.shape[1]:
+            return a
+    return nat.device_tensor(a)
+
+
 def divergence_rows(log_weights, alpha=2.):
     """Device divergence statistics of every row of a [rows, M] log-weight matrix
     (HBM tensor or array) in one launch chain: ndarray [rows, 7] of (d_alpha,
@@ -149,7 +162,7 @@ def divergence_rows(log_weights, alpha=2.):
     `divergence_bound` derives its result and warnings from."""
     if alpha <= 1:
         raise ValueError('alpha must be greater than 1')
-    lw = nat.device_tensor(log_weights)
+    lw = _device_rows(log_weights)
     if lw is None:
         lw = nat.as_f64(np.atleast_2d(np.asarray(log_weights, dtype=float)))
         rows, n = lw.shape
@@ -158,9 +171,7 @@ def divergence_rows(log_weights, alpha=2.):
         if lw.dim() == 1:
             lw = lw.reshape(1, -1)
         rows, n = lw.shape
-        if lw.stride(1) != 1:
-            lw = lw.contiguous()
-        ld = lw.stride(0)
+        ld = lw.stride(0) if rows > 1 else n
     out = np.empty((rows, 7))
     nat.check(nat.lib().vb_divergence_bound_rows(nat.context().handle, nat.dptr(lw), int(rows),
                                                  int(n), int(ld), float(alpha), 0, 0.0,

@@ -199,6 +199,9 @@ __global__ __launch_bounds__(256) void lw_rdev_kernel(const double* lw, long lon
 // reproducible; against numpy's two-pass np.mean / np.std they differ by rounding
 // (as any reduction order at these sizes does).  Each thread streams kDivPer log
 // weights (four loads in flight), so the merges are a small part of the pass.
+// Pass A also keeps the running minimum and whether a nan was read: with a log
+// weight of -inf (and no nan) the statistics of lw are numpy's (mean -inf, standard
+// error nan), as in the three-pass form.
 struct Welf {
   double n, mean, m2;
 };
@@ -269,22 +272,36 @@ __device__ __forceinline__ void div_stream(const double* lw, long long n, F&& f)
 __global__ __launch_bounds__(256) void lw_div_a_kernel(const double* lw, long long n, double* part,
                                                        long long ld) {
   __shared__ Welf red[4];
-  __shared__ double redm[4];
+  __shared__ double redm[4], redn[4];
   lw += (long long)blockIdx.y * ld;
   part += (long long)blockIdx.y * kDivStride;
   Welf a{0.0, 0.0, 0.0};
-  double m = -INFINITY;
+  double m = -INFINITY, lo = INFINITY;
+  bool has_nan = false;
   div_stream(lw, n, [&](double v) {
     m = fmax(m, v);
+    lo = fmin(lo, v);
+    has_nan |= v != v;                 // fmin / fmax skip a nan
     welf_add(a, v);
   });
+  // 2: a nan among the draws, 1: a -inf and no nan, 0: neither; the block's largest
+  double code = has_nan ? 2.0 : (lo == -INFINITY ? 1.0 : 0.0);
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) code = fmax(code, __shfl_down(code, off, 64));
+  if ((threadIdx.x & 63) == 0) redn[threadIdx.x >> 6] = code;   // read after welf_block's barrier
   const Welf b = welf_block<true>(a, m, red, redm);
   if (threadIdx.x == 0) {
+    code = fmax(fmax(redn[0], redn[1]), fmax(redn[2], redn[3]));
+    // a log weight of -inf (a draw outside the target's support): the running mean
+    // turns -inf - -inf = nan at the next finite draw; numpy's two-pass values are
+    // mean = -inf and a nan deviation sum.  With a nan or a +inf among the draws
+    // numpy's mean is nan as well, and the merged state is left as it is.
+    const bool ninf = code == 1.0 && m < INFINITY;
     double* o = part + 4 * blockIdx.x;
     o[0] = m;
     o[1] = b.n;
-    o[2] = b.mean;
-    o[3] = b.m2;
+    o[2] = ninf ? -INFINITY : b.mean;
+    o[3] = ninf ? NAN : b.m2;
   }
 }
 
@@ -293,21 +310,26 @@ __global__ __launch_bounds__(64) void div_a_final(const double* part, int nb, do
   part += (long long)blockIdx.y * kDivStride;
   sc += (long long)blockIdx.y * kDivStride;
   Welf a{0.0, 0.0, 0.0};
-  double m = -INFINITY;
+  // code, as in pass A, from the block means: 2 a nan mean (a nan, or +inf beside
+  // -inf, in that block), 1 a mean of -inf (pass A's override), 0 neither
+  double m = -INFINITY, code = 0.0;
   for (int b = threadIdx.x; b < nb; b += 64) {
     const double* q = part + 4 * b;
     m = fmax(m, q[0]);
+    code = fmax(code, q[2] != q[2] ? 2.0 : (q[2] == -INFINITY ? 1.0 : 0.0));
     a = welf_merge(a, Welf{q[1], q[2], q[3]});
   }
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) {
     a = welf_merge(a, welf_shfl_down(a, off));
     m = fmax(m, __shfl_down(m, off, 64));
+    code = fmax(code, __shfl_down(code, off, 64));
   }
   if (threadIdx.x == 0) {
+    const bool ninf = code == 1.0 && m < INFINITY;
     sc[0] = m;
-    sc[1] = a.mean;
-    sc[2] = a.m2;
+    sc[1] = ninf ? -INFINITY : a.mean;
+    sc[2] = ninf ? NAN : a.m2;
   }
 }
 
@@ -608,6 +630,18 @@ __global__ __launch_bounds__(256) void center_kernel(const double* x, long long 
   if (idx < n * d) xc[idx] = x[idx] - mean[idx % d];
 }
 
+// lower triangle := upper triangle.  The weighted GEMM forms (w xc_i) xc_j, which
+// differs from (w xc_j) xc_i in the last bit; np.cov's matrix is symmetric.  Without
+// weights no mirror is needed: entry (i, j) and entry (j, i) are then the same
+// products xc_i xc_j = xc_j xc_i (multiplication commutes bit for bit) added in the
+// same order over k, so the GEMM's result is symmetric by construction.
+__global__ __launch_bounds__(256) void cov_mirror_kernel(double* cov, long long d) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= d * d) return;
+  const long long i = idx / d, j = idx % d;
+  if (i < j) cov[j * d + i] = cov[i * d + j];
+}
+
 // weights for np.cov(aweights) / np.average: with LOGW, w_i = exp(lw_i - max lw)
 // (improve_with_psis, notebooks/experiments.py:80-82) written to wout after a
 // max pass; partial sums of w and w^2 per block
@@ -747,6 +781,9 @@ hipError_t bounds_weighted_covariance(const double* x, long long n, long long d,
   gm.kscale = wv;
   hipError_t e = gemm(gm, s);
   if (e != hipSuccess) return e;
+  if (w)
+    hipLaunchKernelGGL(cov_mirror_kernel, dim3((unsigned)((d * d + 255) / 256)), dim3(256), 0, s,
+                       cov, d);
   return hipGetLastError();
 }
 
