@@ -1052,10 +1052,22 @@ int vb_family_sample(vb_ctx* c, const vb_family* fam, const double* lam, int64_t
     VB_TRY(dx.stage(c, 2, x_out, nd));
     vbk::FrWork* W;
     VB_TRY(fr_work(c, &W));
-    VB_TRY(vbk::fr_sqrt(W, fi.D, dl.d, c->stream));
-    const double *s, *z;
-    VB_TRY(vbk::fr_draw(W, fi, n, noise_of(noise, host ? dn.d : nullptr), &s, &z, c->stream));
-    VB_TRY(vbk::fr_transform(W, fi.D, n, dl.d, s, z, dx.d, c->stream));
+    // a root that needed more Newton-Schulz iterations than launched (an
+    // ill-conditioned Sigma) runs the call again with a larger count, as
+    // fr_objective does: the status was never read here, and a cold 12-iteration
+    // root at cond(Sigma) ~1e8 came back unconverged (the same draws again: they
+    // depend on the noise descriptor only)
+    for (int attempt = 0;; ++attempt) {
+      VB_TRY(vbk::fr_sqrt(W, fi.D, dl.d, c->stream));
+      const double *s, *z;
+      VB_TRY(vbk::fr_draw(W, fi, n, noise_of(noise, host ? dn.d : nullptr), &s, &z, c->stream));
+      VB_TRY(vbk::fr_transform(W, fi.D, n, dl.d, s, z, dx.d, c->stream));
+      VB_TRY(sync(c));
+      bool again = false;
+      if (int rc = vbk::fr_info(W, c->stream, attempt < 16 ? &again : nullptr)) return rc;
+      if (!again) break;
+    }
+    vbk::fr_retry_done(W);
     VB_TRY(dx.finish(c));
     return sync(c);
   }
