@@ -73,8 +73,12 @@ enum {
 enum vb_family_kind {
   VB_FAMILY_MF_GAUSSIAN = 0, /* lambda = [mean(D), log_std(D)]       vb.py:48-82   */
   VB_FAMILY_MF_T = 1,        /* lambda = [mean(D), log_scale(D)], df  vb.py:140-182 */
-  VB_FAMILY_FR_T = 2         /* lambda = [mu(D), tril(M) row-major (D(D+1)/2)], df;
+  VB_FAMILY_FR_T = 2,        /* lambda = [mu(D), tril(M) row-major (D(D+1)/2)], df;
                                 L = M with exp'd diagonal, Sigma = L L^T  vb.py:192-233 */
+  VB_FAMILY_FR_GAUSSIAN = 3  /* full-rank Gaussian on its Cholesky factor: VB_FAMILY_FR_T's
+                                lambda layout (so either fit initialises the other),
+                                x = mu + L z, entropy D/2 (1 + log 2 pi) + sum M_ii; df is
+                                ignored.  What vb.py:85-137 was meant to be */
 };
 
 enum vb_target_kind {
@@ -207,7 +211,10 @@ typedef struct vb_objective {
  * (24 bits; stride 0 means 1); `step` is the global step index of the first
  * step of the call.  Full-rank t family (VB_FAMILY_FR_T): each step's block of
  * `eps` is [s (N), z (N x D)] with s = sqrt(chisquare(df)/df) and z ~ N(0, I),
- * drawn in that order (vb.py:204-206). */
+ * drawn in that order (vb.py:204-206).  Full-rank Gaussian family
+ * (VB_FAMILY_FR_GAUSSIAN): `eps` is [problem][step][N][D], N(0,1) (vb.py:105); its
+ * Philox draws are the t family's z (counter = column pair d/2, sample, step,
+ * stream; purpose 0), and no s is drawn. */
 typedef struct vb_noise {
   int32_t kind;      /* vb_noise_kind */
   uint32_t stream;

@@ -16,6 +16,9 @@ LIB_PATH = os.environ.get('VIABEL_AMD_LIB') or os.path.join(_HERE, 'libviabel_am
 
 VB_OK, VB_EINVAL, VB_EDEVICE, VB_ENOMEM, VB_EUNSUPPORTED = 0, -1, -2, -3, -4
 FAMILY_MF_GAUSSIAN, FAMILY_MF_T, FAMILY_FR_T = 0, 1, 2
+FAMILY_FR_GAUSSIAN = 3
+# the kinds whose var_param is [mu (D), tril(M) (D (D + 1) / 2)]
+FULL_RANK_FAMILIES = (FAMILY_FR_T, FAMILY_FR_GAUSSIAN)
 TARGET_ISOGAUSS, TARGET_MIXTURE, TARGET_FUNNEL, TARGET_EIGHT_SCHOOLS_NCP = 0, 1, 2, 3
 TARGET_CORR_GAUSS = 4
 TARGET_CALLBACK = 5

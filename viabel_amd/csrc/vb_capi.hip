@@ -522,7 +522,8 @@ struct FamInfo : vbk::Family {
 
 int check_family(const vb_family* f, FamInfo* o) {
   if (!f) return fail(VB_EINVAL, "null vb_family");
-  if (f->kind != VB_FAMILY_MF_GAUSSIAN && f->kind != VB_FAMILY_MF_T && f->kind != VB_FAMILY_FR_T)
+  if (f->kind != VB_FAMILY_MF_GAUSSIAN && f->kind != VB_FAMILY_MF_T && f->kind != VB_FAMILY_FR_T &&
+      f->kind != VB_FAMILY_FR_GAUSSIAN)
     return fail(VB_EUNSUPPORTED, "family kind %d is not implemented on the device", f->kind);
   if (f->dim < 1 || f->dim > (1LL << 30)) return fail(VB_EINVAL, "invalid dimension %lld", (long long)f->dim);
   o->kind = f->kind;
@@ -530,11 +531,16 @@ int check_family(const vb_family* f, FamInfo* o) {
   o->P = 2 * (size_t)f->dim;
   o->df = f->df;
   o->t_scale = o->shape = o->t_const = 0.0;
-  if (f->kind == VB_FAMILY_FR_T) {
-    if (!(f->df > 2)) return fail(VB_EINVAL, "df must be greater than 2");  // vb.py:193-194
+  if (vbk::family_full_rank(f->kind)) {
+    const bool gauss = f->kind == VB_FAMILY_FR_GAUSSIAN;   // df is ignored
+    if (!gauss && !(f->df > 2)) return fail(VB_EINVAL, "df must be greater than 2");  // vb.py:193-194
     if (f->dim > 8192) return fail(VB_EUNSUPPORTED, "full-rank family needs D <= 8192");
     const double D = (double)f->dim;
     o->P = (size_t)f->dim + (size_t)f->dim * (f->dim + 1) / 2;
+    if (gauss) {
+      o->df = 0.0;
+      return VB_OK;
+    }
     // multivariate_t_logpdf constant (_distributions.py:33-34)
     o->t_const = std::lgamma(0.5 * (f->df + D)) - std::lgamma(0.5 * f->df) -
                  0.5 * D * std::log(M_PI * f->df);
@@ -791,7 +797,7 @@ enum class Path {
   ColumnPair,    // fused kernel over column pairs: separable targets at D > kBlockDMax
   Block,         // one workgroup per problem: D <= kBlockDMax
   Materialised,  // mean-field x [N][D] in HBM, one value_grad + update per step (mf_wide_*)
-  FullRank,      // the full-rank t family (fr_*)
+  FullRank,      // the full-rank families: Student-t (fr_*), Cholesky Gaussian (frg_*)
 };
 
 // What decides the path.  A caller leaves out what it does not have: log weights
@@ -806,14 +812,14 @@ struct PathFacts {
 };
 
 int check_pairing(int fam_kind, int tgt_kind) {
-  if (tgt_kind == VB_TARGET_CORR_GAUSS && fam_kind != VB_FAMILY_FR_T)
+  if (tgt_kind == VB_TARGET_CORR_GAUSS && !vbk::family_full_rank(fam_kind))
     return fail(VB_EUNSUPPORTED, "the corr_gauss target is implemented for the full-rank family only");
   return VB_OK;
 }
 
 int choose_path(const PathFacts& f, Path* out) {
   VB_TRY(check_pairing(f.fam, f.tgt));
-  if (f.fam == VB_FAMILY_FR_T) {
+  if (vbk::family_full_rank(f.fam)) {
     *out = Path::FullRank;
     return VB_OK;
   }
@@ -877,7 +883,7 @@ double sep_c0(const FamInfo& fi, bool pd) {
   return pd ? 0.5 * D * std::log(2 * M_PI) : 0.5 * D * (1.0 + std::log(2 * M_PI));
 }
 
-// vb_objective_value_grad for the full-rank t family
+// vb_objective_value_grad for the full-rank families
 int fr_objective(vb_ctx* c, const FamInfo& fi, const vb_target* tgt, const vb_objective* obj,
                  const double* lam, const vb_noise* noise, double* value, double* grad,
                  const TargetHeads& heads) {
@@ -887,7 +893,8 @@ int fr_objective(vb_ctx* c, const FamInfo& fi, const vb_target* tgt, const vb_ob
   In dl, dn;
   Out dg;
   VB_TRY(dl.stage(c, 0, lam, fi.P));
-  if (host) VB_TRY(dn.stage(c, 1, noise->eps, N * fi.D + N));
+  const bool gauss = fi.kind == VB_FAMILY_FR_GAUSSIAN;   // draws are z alone, no scale s
+  if (host) VB_TRY(dn.stage(c, 1, noise->eps, N * fi.D + (gauss ? 0 : N)));
   VB_TRY(dg.stage(c, 2, grad, fi.P));
   const double* tp;
   double tc;
@@ -896,6 +903,14 @@ int fr_objective(vb_ctx* c, const FamInfo& fi, const vb_target* tgt, const vb_ob
   VB_TRY(c->slot[4].reserve(sizeof(double) * 2));
   vbk::FrWork* W;
   VB_TRY(fr_work(c, &W));
+  if (gauss) {
+    VB_TRY(vbk::frg_value_grad(W, make_spec(fi, tgt, obj, tp, tc, heads), dl.d,
+                               noise_of(noise, host ? dn.d : nullptr), c->slot[4].d(), dg.d,
+                               c->stream));
+    VB_HIP(hipMemcpyAsync(value, c->slot[4].p, sizeof(double), hipMemcpyDefault, c->stream));
+    VB_TRY(dg.finish(c));
+    return sync(c);
+  }
   // a root or gradient solve that needed more iterations than launched (an
   // ill-conditioned Sigma) runs the call again with larger counts (fr_info)
   for (int attempt = 0;; ++attempt) {
@@ -1041,17 +1056,23 @@ int vb_family_sample(vb_ctx* c, const vb_family* fam, const double* lam, int64_t
   VB_TRY(check_family(fam, &fi));
   if (!lam || !x_out || !noise || n < 0) return fail(VB_EINVAL, "null argument");
   const size_t nd = (size_t)n * fi.D;
-  if (fi.kind == VB_FAMILY_FR_T) {
+  if (vbk::family_full_rank(fi.kind)) {
     const bool host = noise->kind == VB_NOISE_HOST;
+    const bool gauss = fi.kind == VB_FAMILY_FR_GAUSSIAN;
     if (host && !noise->eps) return fail(VB_EINVAL, "host noise requires eps");
     if (n == 0) return VB_OK;
     In dl, dn;
     Out dx;
     VB_TRY(dl.stage(c, 0, lam, fi.P));
-    if (host) VB_TRY(dn.stage(c, 1, noise->eps, nd + n));
+    if (host) VB_TRY(dn.stage(c, 1, noise->eps, nd + (gauss ? 0 : n)));
     VB_TRY(dx.stage(c, 2, x_out, nd));
     vbk::FrWork* W;
     VB_TRY(fr_work(c, &W));
+    if (gauss) {
+      VB_TRY(vbk::frg_sample(W, fi, dl.d, n, noise_of(noise, host ? dn.d : nullptr), dx.d, c->stream));
+      VB_TRY(dx.finish(c));
+      return sync(c);
+    }
     // a root that needed more Newton-Schulz iterations than launched (an
     // ill-conditioned Sigma) runs the call again with a larger count, as
     // fr_objective does: the status was never read here, and a cold 12-iteration
@@ -1095,14 +1116,17 @@ int vb_family_logdensity(vb_ctx* c, const vb_family* fam, const double* lam, con
   if (!lam || !x || !out || n < 0) return fail(VB_EINVAL, "null argument");
   In dl, dxx;
   Out dout;
-  if (fi.kind == VB_FAMILY_FR_T) {
+  if (vbk::family_full_rank(fi.kind)) {
     if (n == 0) return VB_OK;
     VB_TRY(dl.stage(c, 0, lam, fi.P));
     VB_TRY(dxx.stage(c, 1, x, (size_t)n * fi.D));
     VB_TRY(dout.stage(c, 2, out, (size_t)n));
     vbk::FrWork* W;
     VB_TRY(fr_work(c, &W));
-    VB_TRY(vbk::fr_logdensity(W, fi, dl.d, dxx.d, n, dout.d, c->stream));
+    if (fi.kind == VB_FAMILY_FR_GAUSSIAN)
+      VB_TRY(vbk::frg_logdensity(W, fi, dl.d, dxx.d, n, dout.d, c->stream));
+    else
+      VB_TRY(vbk::fr_logdensity(W, fi, dl.d, dxx.d, n, dout.d, c->stream));
     VB_TRY(dout.finish(c));
     return sync(c);
   }
@@ -1120,7 +1144,7 @@ int vb_family_moments(vb_ctx* c, const vb_family* fam, const double* lam, double
   FamInfo fi;
   VB_TRY(check_family(fam, &fi));
   if (!lam) return fail(VB_EINVAL, "null argument");
-  if (fi.kind != VB_FAMILY_FR_T)
+  if (!vbk::family_full_rank(fi.kind))
     return fail(VB_EUNSUPPORTED, "vb_family_moments is for the full-rank family");
   const size_t dd = (size_t)fi.D * fi.D;
   In dl;
@@ -1447,7 +1471,8 @@ int vb_run_create(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const v
 static int advance_fr_steps(vb_ctx* c, vb_run* r, int64_t n_steps, const vbk::Noise& nz) {
   const size_t P = r->fi.P;
   const bool fr = r->path == Path::FullRank;
-  const size_t per_step = (size_t)r->N * r->fi.D + (fr ? (size_t)r->N : 0);
+  const bool frg = fr && r->fi.kind == VB_FAMILY_FR_GAUSSIAN;
+  const size_t per_step = (size_t)r->N * r->fi.D + (fr && !frg ? (size_t)r->N : 0);
   vbk::FrWork* W;
   VB_TRY(fr_work(c, &W));
   for (long long off = 0; off < n_steps; ++off) {
@@ -1462,7 +1487,13 @@ static int advance_fr_steps(vb_ctx* c, vb_run* r, int64_t n_steps, const vbk::No
                          : nullptr;
       double* value = r->values.d() + q * r->n_iters + step;
       const vbk::MfUpdate up{r->ring.d() + q * P * r->W, r->W, step, lr, r->eps, hrow};
-      if (fr) {
+      if (frg) {
+        // Philox draws: the adagrad step rides in the gradient kernel's epilogue (vb_frg.hip)
+        const bool fuse = !nz.eps && r->opt == VB_OPT_ADAGRAD;
+        VB_TRY(vbk::frg_value_grad(W, r->spec, lam, nq, value, r->grad.d(), c->stream,
+                                   fuse ? &up : nullptr));
+        if (fuse) continue;
+      } else if (fr) {
         // one problem with Philox draws: the adagrad step rides in the step's last
         // kernel, which also prepares the next step of this advance (vb_fr.hip)
         const bool fuse = r->nprob == 1 && !nz.eps && r->opt == VB_OPT_ADAGRAD && fr_fuse_enabled();
@@ -1500,7 +1531,7 @@ static int advance_materialised(vb_ctx* c, vb_run* r, int64_t n_steps, const vbk
   // fr_info)
   // (and the workspace's warm state: the rerun's first step starts from the
   // same previous root, power vectors and schedule as the failed pass did)
-  const bool snap = fr && r->nprob == 1;
+  const bool snap = fr && r->fi.kind == VB_FAMILY_FR_T && r->nprob == 1;
   const size_t snap_n = P + P * (size_t)r->W;
   vbk::FrWork* W = nullptr;
   if (fr) VB_TRY(fr_work(c, &W));
@@ -1691,7 +1722,8 @@ int vb_run_advance(vb_run* r, int64_t n_steps, const vb_noise* noise) {
   if (host) {
     if (!noise->eps) return fail(VB_EINVAL, "host noise requires eps");
     if (ptr_class(noise->eps) < 0) return foreign_ptr_error(noise->eps);
-    const size_t per_step = (size_t)r->N * r->fi.D + (fr ? (size_t)r->N : 0);
+    const size_t per_step =
+        (size_t)r->N * r->fi.D + (fr && r->fi.kind == VB_FAMILY_FR_T ? (size_t)r->N : 0);
     const size_t tot = per_step * n_steps * r->nprob;
     if (is_device_ptr(noise->eps)) {
       // used in place
@@ -1959,7 +1991,7 @@ int vb_log_weights_rows(vb_ctx* c, const vb_family* fam, const vb_target* tgt,
   VB_TRY(check_target(tgt, fi.D));
   if (!lam || !noise || !lw_out || m < 0 || rows < 0) return fail(VB_EINVAL, "null argument");
   if (rows > 65535) return fail(VB_EINVAL, "rows must be <= 65535");
-  if (fi.kind == VB_FAMILY_FR_T) return fail(VB_EUNSUPPORTED, "rows of log weights: mean-field families only");
+  if (vbk::family_full_rank(fi.kind)) return fail(VB_EUNSUPPORTED, "rows of log weights: mean-field families only");
   if (noise->kind != VB_NOISE_PHILOX) return fail(VB_EINVAL, "rows of log weights need Philox noise");
   // (a pairing choose_path rejects has no rows kernel either)
   Path path;
@@ -1996,8 +2028,9 @@ int vb_log_weights(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const 
   In dl, dn;
   Out dlw, dxs;
   VB_TRY(dl.stage(c, 0, lam, fi.P));
-  // full rank: each draw carries its scale s beside z
-  if (host) VB_TRY(dn.stage(c, 1, noise->eps, (size_t)m * fi.D + (fr ? m : 0)));
+  // full-rank t: each draw carries its scale s beside z
+  const bool frg = fr && fi.kind == VB_FAMILY_FR_GAUSSIAN;
+  if (host) VB_TRY(dn.stage(c, 1, noise->eps, (size_t)m * fi.D + (fr && !frg ? m : 0)));
   VB_TRY(dlw.stage(c, 2, lw_out, (size_t)m));
   VB_TRY(dxs.stage(c, 3, samples_out, samples_out ? (size_t)m * fi.D : 0));
   const vbk::Noise nz = noise_of(noise, host ? dn.d : nullptr);
@@ -2011,7 +2044,9 @@ int vb_log_weights(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const 
     vbk::FrWork* W;
     VB_TRY(fr_work(c, &W));
     const vbk::Spec f = make_spec(fi, tgt, nullptr, tp, tc, heads);
-    if (fr)
+    if (frg)
+      VB_TRY(vbk::frg_log_weights(W, f, dl.d, m, nz, dlw.d, dxs.d, c->stream));
+    else if (fr)
       VB_TRY(vbk::fr_log_weights(W, f, dl.d, m, nz, dlw.d, dxs.d, c->stream));
     else
       VB_TRY(vbk::mf_wide_log_weights(W, f, dl.d, m, nz, dlw.d, dxs.d, c->stream));

@@ -1606,6 +1606,24 @@ int eval_target(FrWork* W, const Spec& f, int D, long long n, const double* x, d
 }
 }  // namespace
 
+// The workspace's row buffers for n rows of dimension D (vb_frg.hip).  The t
+// family's prepared next step is dropped: its draws live in the same buffers.
+int fr_rows(FrWork* W, int D, long long n, FrRows* out) {
+  W->prep_owner = nullptr;
+  if (int rc = reserve_n(W, D, n)) return rc;
+  FR_HIP(W->scal.reserve(sizeof(double) * 8));
+  *out = FrRows{W->Z.d(), W->X.d(), W->G.d(), W->logp.d(), W->zz.d(), W->scal.d()};
+  return 0;
+}
+
+// log p [n] and (grad non-null) its gradient [n][D] of any target at x [n][D]
+int fr_eval_target(FrWork* W, const Spec& f, long long n, const double* x, double* logp,
+                   double* grad, hipStream_t st) {
+  if (f.tgt == kTargetCorrGauss)
+    return fr_target(W, f.tgt, f.fam.D, n, f.tparams, f.tconst, x, logp, grad, st);
+  return eval_target(W, f, f.fam.D, n, x, logp, grad, st);
+}
+
 // L, eigh(L L^T) -> (w ascending, Vt rows = eigenvectors), half log det from the
 // eigenvalues (multivariate_t_logpdf's log_pdet, _distributions.py:27-32)
 int fr_prepare(FrWork* W, int D, const double* lam, hipStream_t st) {

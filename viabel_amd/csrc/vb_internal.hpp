@@ -373,4 +373,30 @@ void fr_retry_done(FrWork* W);
 hipError_t launch_fr_lw(const Family& f, long long m, const double* logp, const double* zz,
                         const double* s, const double* scal, double* lw, hipStream_t st);
 
+// ---- full-rank Gaussian family on its Cholesky factor (vb_frg.hip) -------------
+constexpr int kFamilyFrGaussian = 3;
+// Both full-rank kinds share the parameter layout [mu (D), tril(M) (D(D+1)/2)].
+inline bool family_full_rank(int kind) { return kind == kFamilyFrT || kind == kFamilyFrGaussian; }
+// The workspace's row buffers, reserved for n rows of dimension D: draws Z [n][D],
+// samples X [n][D], target gradient G [n][D], logp / zz [n] and 8 scalars.  Taking
+// them drops the t family's prepared next step (FrWork::prep_owner).
+struct FrRows {
+  double *Z, *X, *G, *logp, *zz, *scal;
+};
+int fr_rows(FrWork* W, int D, long long n, FrRows* out);
+// eval_target for every target kind (corr_gauss through fr_target)
+int fr_eval_target(FrWork* W, const Spec& f, long long n, const double* x, double* logp,
+                   double* grad, hipStream_t st);
+// nz.eps (host draws) = z [n][D] on the device, N(0,1)
+int frg_sample(FrWork* W, const Family& f, const double* lam, long long n, const Noise& nz,
+               double* x, hipStream_t st);
+// up (non-null): the windowed adagrad step is fused into the gradient kernel's
+// epilogue (lam updated in place, ring / history row written, grad untouched)
+int frg_value_grad(FrWork* W, const Spec& f, const double* lam, const Noise& nz, double* value,
+                   double* grad, hipStream_t st, const MfUpdate* up = nullptr);
+int frg_logdensity(FrWork* W, const Family& f, const double* lam, const double* x, long long n,
+                   double* out, hipStream_t st);
+int frg_log_weights(FrWork* W, const Spec& f, const double* lam, long long m, const Noise& nz,
+                    double* lw, double* xs, hipStream_t st);
+
 }  // namespace vbk

@@ -6,6 +6,7 @@ error messages) for the hot path:
   mean_field_gaussian_variational_family  vb.py:48-82
   mean_field_t_variational_family         vb.py:140-182
   t_variational_family (full rank)        vb.py:185-233, _distributions.py:8-38
+  cholesky_gaussian_variational_family    what vb.py:85-137 was meant to be
   black_box_klvi                          vb.py:236-245
   black_box_chivi                         vb.py:248-266
   black_box_klvi_pd / black_box_klvi_pd2  vb.py:268-295
@@ -44,6 +45,7 @@ __all__ = [
     'mean_field_gaussian_variational_family',
     'mean_field_t_variational_family',
     'full_rank_gaussian_variational_family',
+    'cholesky_gaussian_variational_family',
     't_variational_family',
     'black_box_klvi',
     'black_box_chivi',
@@ -95,8 +97,8 @@ class NativeVariationalFamily(VariationalFamily):
     # standardized draws exactly as the reference draws them
     def _draw(self, n, seed=None):
         rs = self.rs if seed is None else np.random.RandomState(seed)
-        if self.kind == nat.FAMILY_MF_GAUSSIAN:
-            return rs.randn(n, self.dim)
+        if self.kind in (nat.FAMILY_MF_GAUSSIAN, nat.FAMILY_FR_GAUSSIAN):
+            return rs.randn(n, self.dim)                              # vb.py:52 / 105
         if self.kind == nat.FAMILY_FR_T:
             # vb.py:204-206: chisquare first, then randn; flat [s (n), z (n x D)]
             s = np.sqrt(rs.chisquare(self.df, n) / self.df)
@@ -275,13 +277,90 @@ def mean_field_gaussian_variational_family(dim, rng=None):
     return _make_family(nat.FAMILY_MF_GAUSSIAN, dim, None, rng)
 
 
+def cholesky_gaussian_variational_family(dim, rng=None):
+    """Full-rank Gaussian on its Cholesky factor: what vb.py:85-137 was meant to
+    be.  var_param = [mu (dim), tril(M) (dim (dim + 1) / 2)], t_variational_family's
+    layout (row-major lower triangle, log diagonal), L = M with its diagonal
+    exponentiated, Sigma = L L^T; a t fit initialises a Gaussian fit and the
+    reverse.  sample is x = mu + z L^T with z = randn(n, dim) from the family's
+    RandomState(0) (vb.py:105) or, with rng='philox', the t family's z draws; the
+    entropy is D/2 (1 + log 2 pi) + sum M_ii."""
+    rng = _DEFAULT_RNG[0] if rng is None else rng
+    if rng not in ('numpy', 'philox'):
+        raise ValueError("rng must be 'numpy' or 'philox'")
+    dim = int(dim)
+    P = dim + dim * (dim + 1) // 2
+    diag = dim + np.arange(1, dim + 1) * np.arange(2, dim + 2) // 2 - 1   # M_ii in var_param
+
+    def _lam(var_param):
+        lam = nat.as_f64(var_param)
+        if lam.shape != (P,):
+            raise ValueError('var_param must have shape (%d,)' % P)
+        return lam
+
+    def sample(var_param, n_samples, seed=None):
+        lam = _lam(var_param)
+        out = np.empty((int(n_samples), dim))
+        if fam.rng == 'numpy':
+            eps = nat.as_f64(fam._draw(int(n_samples), seed))
+            nz = nat.Noise(nat.NOISE_HOST, 0, 0, 0, nat.dptr(eps))
+        else:
+            nz = fam._philox_noise(seed)
+        nat.check(nat.lib().vb_family_sample(nat.context().handle, fam._struct(), nat.dptr(lam),
+                                             int(n_samples), nz, nat.dptr(out)))
+        return out
+
+    def logdensity(x, var_param):
+        lam = _lam(var_param)
+        xx = np.asarray(x, dtype=float)
+        one_d = xx.ndim == 1
+        xx = nat.as_f64(np.atleast_2d(xx))
+        if xx.shape[1] != dim:
+            raise ValueError('x must have %d columns' % dim)
+        out = np.empty(xx.shape[0])
+        nat.check(nat.lib().vb_family_logdensity(nat.context().handle, fam._struct(),
+                                                 nat.dptr(lam), nat.dptr(xx), xx.shape[0],
+                                                 nat.dptr(out)))
+        return out[0] if one_d else out
+
+    def entropy(var_param):
+        lam = _lam(var_param)
+        return 0.5 * dim * (1.0 + LOG2PI) + np.sum(lam[diag])
+
+    def _sigma(lam):
+        sig = np.empty((dim, dim))
+        nat.check(nat.lib().vb_family_moments(nat.context().handle, fam._struct(), nat.dptr(lam),
+                                              nat.dptr(sig), None))
+        return sig
+
+    def mean_and_cov(var_param):
+        lam = _lam(var_param)
+        return lam[:dim].copy(), _sigma(lam)
+
+    def pth_moment(p, var_param):
+        if p not in [2, 4]:
+            raise ValueError('only p = 2 or 4 supported')
+        sig = _sigma(_lam(var_param))
+        tr = np.trace(sig)
+        if p == 2:
+            return tr
+        return 2 * np.sum(sig ** 2) + tr ** 2
+
+    fam = NativeVariationalFamily(sample, entropy, logdensity, mean_and_cov, pth_moment, P)
+    fam.kind, fam.dim, fam.df, fam.rng = nat.FAMILY_FR_GAUSSIAN, dim, None, rng
+    fam.seed, fam.stream, fam.step = 0, next(_STREAMS) & 0xFFFFFF, 0
+    return fam
+
+
 def full_rank_gaussian_variational_family(dim):
     """Importable for the reference notebooks' import cells (vb.py:85-137); not
-    built: the reference's own version is broken, and the
-    full-rank path here is t_variational_family (a large df approaches it)."""
+    built under this name: the reference's own version is broken (SURVEY §2,
+    DESIGN §8).  The working full-rank Gaussian is
+    cholesky_gaussian_variational_family, on the Cholesky factor the reference's
+    version was meant to use."""
     raise NotImplementedError(
-        'full_rank_gaussian_variational_family is out of scope for viabel_amd; '
-        'use t_variational_family(dim, df) with a large df')
+        'full_rank_gaussian_variational_family is the reference\'s broken family and is '
+        'not built; use cholesky_gaussian_variational_family(dim)')
 
 
 def mean_field_t_variational_family(dim, df, rng=None):
