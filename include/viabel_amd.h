@@ -75,10 +75,15 @@ enum vb_family_kind {
   VB_FAMILY_MF_T = 1,        /* lambda = [mean(D), log_scale(D)], df  vb.py:140-182 */
   VB_FAMILY_FR_T = 2,        /* lambda = [mu(D), tril(M) row-major (D(D+1)/2)], df;
                                 L = M with exp'd diagonal, Sigma = L L^T  vb.py:192-233 */
-  VB_FAMILY_FR_GAUSSIAN = 3  /* full-rank Gaussian on its Cholesky factor: VB_FAMILY_FR_T's
+  VB_FAMILY_FR_GAUSSIAN = 3, /* full-rank Gaussian on its Cholesky factor: VB_FAMILY_FR_T's
                                 lambda layout (so either fit initialises the other),
                                 x = mu + L z, entropy D/2 (1 + log 2 pi) + sum M_ii; df is
                                 ignored.  What vb.py:85-137 was meant to be */
+  VB_FAMILY_LR_GAUSSIAN = 4  /* low-rank-plus-diagonal Gaussian, Sigma = B B^T + diag(d^2):
+                                lambda = [mu(D), log_d(D), B row-major (D x R)], d = exp(log_d),
+                                R = vb_family.rank with 1 <= R <= min(D, 64);
+                                x = mu + d z + B u, entropy D/2 (1 + log 2 pi) + sum log_d +
+                                1/2 log det(I + W^T W), W = diag(1/d) B; df is ignored */
 };
 
 enum vb_target_kind {
@@ -182,7 +187,7 @@ enum vb_noise_kind {
 
 typedef struct vb_family {
   int32_t kind;   /* vb_family_kind */
-  int32_t reserved;
+  int32_t rank;   /* R of VB_FAMILY_LR_GAUSSIAN; ignored for the other kinds */
   int64_t dim;    /* D */
   double df;      /* degrees of freedom (t family), ignored otherwise */
 } vb_family;
@@ -214,7 +219,10 @@ typedef struct vb_objective {
  * drawn in that order (vb.py:204-206).  Full-rank Gaussian family
  * (VB_FAMILY_FR_GAUSSIAN): `eps` is [problem][step][N][D], N(0,1) (vb.py:105); its
  * Philox draws are the t family's z (counter = column pair d/2, sample, step,
- * stream; purpose 0), and no s is drawn. */
+ * stream; purpose 0), and no s is drawn.  Low-rank Gaussian family
+ * (VB_FAMILY_LR_GAUSSIAN): `eps` is [problem][step][N][D + R], N(0,1), each row
+ * [z (D), u (R)]; its Philox draws are the same z row at width D + R.
+ * vb_family_moments and rows of log weights do not take this kind. */
 typedef struct vb_noise {
   int32_t kind;      /* vb_noise_kind */
   uint32_t stream;

@@ -17,8 +17,11 @@ LIB_PATH = os.environ.get('VIABEL_AMD_LIB') or os.path.join(_HERE, 'libviabel_am
 VB_OK, VB_EINVAL, VB_EDEVICE, VB_ENOMEM, VB_EUNSUPPORTED = 0, -1, -2, -3, -4
 FAMILY_MF_GAUSSIAN, FAMILY_MF_T, FAMILY_FR_T = 0, 1, 2
 FAMILY_FR_GAUSSIAN = 3
+FAMILY_LR_GAUSSIAN = 4    # var_param = [mu (D), log_d (D), B (D x rank)]
 # the kinds whose var_param is [mu (D), tril(M) (D (D + 1) / 2)]
 FULL_RANK_FAMILIES = (FAMILY_FR_T, FAMILY_FR_GAUSSIAN)
+# the kinds with correlations: no rows of log weights, their own moments per restart
+CORRELATED_FAMILIES = FULL_RANK_FAMILIES + (FAMILY_LR_GAUSSIAN,)
 TARGET_ISOGAUSS, TARGET_MIXTURE, TARGET_FUNNEL, TARGET_EIGHT_SCHOOLS_NCP = 0, 1, 2, 3
 TARGET_CORR_GAUSS = 4
 TARGET_CALLBACK = 5
@@ -34,7 +37,8 @@ c_int64_p = ctypes.POINTER(ctypes.c_int64)
 
 
 class Family(ctypes.Structure):
-    _fields_ = [('kind', ctypes.c_int32), ('reserved', ctypes.c_int32),
+    # rank: R of FAMILY_LR_GAUSSIAN, ignored for the other kinds
+    _fields_ = [('kind', ctypes.c_int32), ('rank', ctypes.c_int32),
                 ('dim', ctypes.c_int64), ('df', ctypes.c_double)]
 
 

@@ -523,7 +523,7 @@ struct FamInfo : vbk::Family {
 int check_family(const vb_family* f, FamInfo* o) {
   if (!f) return fail(VB_EINVAL, "null vb_family");
   if (f->kind != VB_FAMILY_MF_GAUSSIAN && f->kind != VB_FAMILY_MF_T && f->kind != VB_FAMILY_FR_T &&
-      f->kind != VB_FAMILY_FR_GAUSSIAN)
+      f->kind != VB_FAMILY_FR_GAUSSIAN && f->kind != VB_FAMILY_LR_GAUSSIAN)
     return fail(VB_EUNSUPPORTED, "family kind %d is not implemented on the device", f->kind);
   if (f->dim < 1 || f->dim > (1LL << 30)) return fail(VB_EINVAL, "invalid dimension %lld", (long long)f->dim);
   o->kind = f->kind;
@@ -531,6 +531,15 @@ int check_family(const vb_family* f, FamInfo* o) {
   o->P = 2 * (size_t)f->dim;
   o->df = f->df;
   o->t_scale = o->shape = o->t_const = 0.0;
+  o->R = 0;   // vb_family.rank is read for the low-rank Gaussian only
+  if (f->kind == VB_FAMILY_LR_GAUSSIAN) {
+    if (f->rank < 1 || f->rank > vbk::kLrgRankMax || f->rank > f->dim)
+      return fail(VB_EINVAL, "rank must be between 1 and min(dim, %d)", vbk::kLrgRankMax);
+    o->R = f->rank;
+    o->P = (size_t)f->dim * ((size_t)f->rank + 2);   // mu, log_d, B [D][R]
+    o->df = 0.0;                                     // ignored
+    return VB_OK;
+  }
   if (vbk::family_full_rank(f->kind)) {
     const bool gauss = f->kind == VB_FAMILY_FR_GAUSSIAN;   // df is ignored
     if (!gauss && !(f->df > 2)) return fail(VB_EINVAL, "df must be greater than 2");  // vb.py:193-194
@@ -798,7 +807,12 @@ enum class Path {
   Block,         // one workgroup per problem: D <= kBlockDMax
   Materialised,  // mean-field x [N][D] in HBM, one value_grad + update per step (mf_wide_*)
   FullRank,      // the full-rank families: Student-t (fr_*), Cholesky Gaussian (frg_*)
+  LowRank,       // the low-rank-plus-diagonal Gaussian (lrg_*)
 };
+
+// The paths of the families that bring their own step kernels: one value_grad per step
+// and problem on the shared row workspace (advance_fr_steps).
+inline bool family_path(Path p) { return p == Path::FullRank || p == Path::LowRank; }
 
 // What decides the path.  A caller leaves out what it does not have: log weights
 // have no objective, and a single value-and-gradient call has no optimiser, window
@@ -812,7 +826,8 @@ struct PathFacts {
 };
 
 int check_pairing(int fam_kind, int tgt_kind) {
-  if (tgt_kind == VB_TARGET_CORR_GAUSS && !vbk::family_full_rank(fam_kind))
+  if (tgt_kind == VB_TARGET_CORR_GAUSS && !vbk::family_full_rank(fam_kind) &&
+      fam_kind != VB_FAMILY_LR_GAUSSIAN)
     return fail(VB_EUNSUPPORTED, "the corr_gauss target is implemented for the full-rank family only");
   return VB_OK;
 }
@@ -821,6 +836,10 @@ int choose_path(const PathFacts& f, Path* out) {
   VB_TRY(check_pairing(f.fam, f.tgt));
   if (vbk::family_full_rank(f.fam)) {
     *out = Path::FullRank;
+    return VB_OK;
+  }
+  if (f.fam == VB_FAMILY_LR_GAUSSIAN) {   // any target, objective and optimiser
+    *out = Path::LowRank;
     return VB_OK;
   }
   const bool wide = f.D > vbk::kBlockDMax;
@@ -894,7 +913,7 @@ int fr_objective(vb_ctx* c, const FamInfo& fi, const vb_target* tgt, const vb_ob
   Out dg;
   VB_TRY(dl.stage(c, 0, lam, fi.P));
   const bool gauss = fi.kind == VB_FAMILY_FR_GAUSSIAN;   // draws are z alone, no scale s
-  if (host) VB_TRY(dn.stage(c, 1, noise->eps, N * fi.D + (gauss ? 0 : N)));
+  if (host) VB_TRY(dn.stage(c, 1, noise->eps, N * vbk::family_noise_width(fi)));
   VB_TRY(dg.stage(c, 2, grad, fi.P));
   const double* tp;
   double tc;
@@ -903,10 +922,13 @@ int fr_objective(vb_ctx* c, const FamInfo& fi, const vb_target* tgt, const vb_ob
   VB_TRY(c->slot[4].reserve(sizeof(double) * 2));
   vbk::FrWork* W;
   VB_TRY(fr_work(c, &W));
-  if (gauss) {
-    VB_TRY(vbk::frg_value_grad(W, make_spec(fi, tgt, obj, tp, tc, heads), dl.d,
-                               noise_of(noise, host ? dn.d : nullptr), c->slot[4].d(), dg.d,
-                               c->stream));
+  if (gauss || fi.kind == VB_FAMILY_LR_GAUSSIAN) {
+    const vbk::Spec f = make_spec(fi, tgt, obj, tp, tc, heads);
+    const vbk::Noise nz = noise_of(noise, host ? dn.d : nullptr);
+    if (gauss)
+      VB_TRY(vbk::frg_value_grad(W, f, dl.d, nz, c->slot[4].d(), dg.d, c->stream));
+    else
+      VB_TRY(vbk::lrg_value_grad(W, f, dl.d, nz, c->slot[4].d(), dg.d, c->stream));
     VB_HIP(hipMemcpyAsync(value, c->slot[4].p, sizeof(double), hipMemcpyDefault, c->stream));
     VB_TRY(dg.finish(c));
     return sync(c);
@@ -1056,7 +1078,7 @@ int vb_family_sample(vb_ctx* c, const vb_family* fam, const double* lam, int64_t
   VB_TRY(check_family(fam, &fi));
   if (!lam || !x_out || !noise || n < 0) return fail(VB_EINVAL, "null argument");
   const size_t nd = (size_t)n * fi.D;
-  if (vbk::family_full_rank(fi.kind)) {
+  if (vbk::family_full_rank(fi.kind) || fi.kind == VB_FAMILY_LR_GAUSSIAN) {
     const bool host = noise->kind == VB_NOISE_HOST;
     const bool gauss = fi.kind == VB_FAMILY_FR_GAUSSIAN;
     if (host && !noise->eps) return fail(VB_EINVAL, "host noise requires eps");
@@ -1064,10 +1086,15 @@ int vb_family_sample(vb_ctx* c, const vb_family* fam, const double* lam, int64_t
     In dl, dn;
     Out dx;
     VB_TRY(dl.stage(c, 0, lam, fi.P));
-    if (host) VB_TRY(dn.stage(c, 1, noise->eps, nd + (gauss ? 0 : n)));
+    if (host) VB_TRY(dn.stage(c, 1, noise->eps, (size_t)n * vbk::family_noise_width(fi)));
     VB_TRY(dx.stage(c, 2, x_out, nd));
     vbk::FrWork* W;
     VB_TRY(fr_work(c, &W));
+    if (fi.kind == VB_FAMILY_LR_GAUSSIAN) {
+      VB_TRY(vbk::lrg_sample(W, fi, dl.d, n, noise_of(noise, host ? dn.d : nullptr), dx.d, c->stream));
+      VB_TRY(dx.finish(c));
+      return sync(c);
+    }
     if (gauss) {
       VB_TRY(vbk::frg_sample(W, fi, dl.d, n, noise_of(noise, host ? dn.d : nullptr), dx.d, c->stream));
       VB_TRY(dx.finish(c));
@@ -1116,14 +1143,16 @@ int vb_family_logdensity(vb_ctx* c, const vb_family* fam, const double* lam, con
   if (!lam || !x || !out || n < 0) return fail(VB_EINVAL, "null argument");
   In dl, dxx;
   Out dout;
-  if (vbk::family_full_rank(fi.kind)) {
+  if (vbk::family_full_rank(fi.kind) || fi.kind == VB_FAMILY_LR_GAUSSIAN) {
     if (n == 0) return VB_OK;
     VB_TRY(dl.stage(c, 0, lam, fi.P));
     VB_TRY(dxx.stage(c, 1, x, (size_t)n * fi.D));
     VB_TRY(dout.stage(c, 2, out, (size_t)n));
     vbk::FrWork* W;
     VB_TRY(fr_work(c, &W));
-    if (fi.kind == VB_FAMILY_FR_GAUSSIAN)
+    if (fi.kind == VB_FAMILY_LR_GAUSSIAN)
+      VB_TRY(vbk::lrg_logdensity(W, fi, dl.d, dxx.d, n, dout.d, c->stream));
+    else if (fi.kind == VB_FAMILY_FR_GAUSSIAN)
       VB_TRY(vbk::frg_logdensity(W, fi, dl.d, dxx.d, n, dout.d, c->stream));
     else
       VB_TRY(vbk::fr_logdensity(W, fi, dl.d, dxx.d, n, dout.d, c->stream));
@@ -1235,7 +1264,7 @@ int vb_objective_value_grad(vb_ctx* c, const vb_family* fam, const vb_target* tg
     return fail(VB_EINVAL, "alpha must be positive");
   Path path;
   VB_TRY(choose_path({fi.kind, tgt->kind, fi.D, obj->kind}, &path));
-  if (path == Path::FullRank) return fr_objective(c, fi, tgt, obj, lam, noise, value, grad, heads);
+  if (family_path(path)) return fr_objective(c, fi, tgt, obj, lam, noise, value, grad, heads);
   const int D = fi.D, N = (int)obj->n_samples;
   const size_t P = 2 * (size_t)D;
   const bool host = noise->kind == VB_NOISE_HOST;
@@ -1393,7 +1422,7 @@ int vb_run_create(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const v
   Path path;
   VB_TRY(choose_path({fi.kind, tgt->kind, fi.D, obj->kind, cfg->optimizer, cfg->window, n_problems},
                      &path));
-  const bool fr = path == Path::FullRank, wide = path == Path::Materialised;
+  const bool fr = family_path(path), wide = path == Path::Materialised;
 
   vb_run* r = new (std::nothrow) vb_run();
   if (!r) return fail(VB_ENOMEM, "out of host memory");
@@ -1470,9 +1499,10 @@ int vb_run_create(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const v
 // update per step and problem), for steps [r->done, r->done + n_steps).
 static int advance_fr_steps(vb_ctx* c, vb_run* r, int64_t n_steps, const vbk::Noise& nz) {
   const size_t P = r->fi.P;
-  const bool fr = r->path == Path::FullRank;
+  const bool fr = family_path(r->path);
   const bool frg = fr && r->fi.kind == VB_FAMILY_FR_GAUSSIAN;
-  const size_t per_step = (size_t)r->N * r->fi.D + (fr && !frg ? (size_t)r->N : 0);
+  const bool lrg = r->path == Path::LowRank;
+  const size_t per_step = (size_t)r->N * (fr ? vbk::family_noise_width(r->fi) : (size_t)r->fi.D);
   vbk::FrWork* W;
   VB_TRY(fr_work(c, &W));
   for (long long off = 0; off < n_steps; ++off) {
@@ -1487,11 +1517,16 @@ static int advance_fr_steps(vb_ctx* c, vb_run* r, int64_t n_steps, const vbk::No
                          : nullptr;
       double* value = r->values.d() + q * r->n_iters + step;
       const vbk::MfUpdate up{r->ring.d() + q * P * r->W, r->W, step, lr, r->eps, hrow};
-      if (frg) {
-        // Philox draws: the adagrad step rides in the gradient kernel's epilogue (vb_frg.hip)
+      if (frg || lrg) {
+        // Philox draws: the adagrad step rides in the gradient kernel's epilogue
+        // (vb_frg.hip, vb_lrg.hip)
         const bool fuse = !nz.eps && r->opt == VB_OPT_ADAGRAD;
-        VB_TRY(vbk::frg_value_grad(W, r->spec, lam, nq, value, r->grad.d(), c->stream,
-                                   fuse ? &up : nullptr));
+        if (lrg)
+          VB_TRY(vbk::lrg_value_grad(W, r->spec, lam, nq, value, r->grad.d(), c->stream,
+                                     fuse ? &up : nullptr));
+        else
+          VB_TRY(vbk::frg_value_grad(W, r->spec, lam, nq, value, r->grad.d(), c->stream,
+                                     fuse ? &up : nullptr));
         if (fuse) continue;
       } else if (fr) {
         // one problem with Philox draws: the adagrad step rides in the step's last
@@ -1524,7 +1559,7 @@ static int advance_fr_steps(vb_ctx* c, vb_run* r, int64_t n_steps, const vbk::No
 // vb_run_advance on the full-rank / materialised paths
 static int advance_materialised(vb_ctx* c, vb_run* r, int64_t n_steps, const vbk::Noise& nz) {
   const size_t P = r->fi.P;
-  const bool fr = r->path == Path::FullRank;
+  const bool fr = family_path(r->path);
   // one full-rank problem: a snapshot of lambda and the adagrad window lets the
   // advance run again when a warm Newton-Schulz root launched too few
   // iterations (they launch exactly the learnt count, no spares; vb_fr.hip
@@ -1718,12 +1753,12 @@ int vb_run_advance(vb_run* r, int64_t n_steps, const vb_noise* noise) {
                 (long long)r->n_iters, (long long)r->done);
   if (n_steps == 0) return VB_OK;
   const bool host = noise->kind == VB_NOISE_HOST;
-  const bool fr = r->path == Path::FullRank;
+  const bool fr = family_path(r->path);
   if (host) {
     if (!noise->eps) return fail(VB_EINVAL, "host noise requires eps");
     if (ptr_class(noise->eps) < 0) return foreign_ptr_error(noise->eps);
     const size_t per_step =
-        (size_t)r->N * r->fi.D + (fr && r->fi.kind == VB_FAMILY_FR_T ? (size_t)r->N : 0);
+        (size_t)r->N * (fr ? vbk::family_noise_width(r->fi) : (size_t)r->fi.D);
     const size_t tot = per_step * n_steps * r->nprob;
     if (is_device_ptr(noise->eps)) {
       // used in place
@@ -1744,6 +1779,7 @@ int vb_run_advance(vb_run* r, int64_t n_steps, const vb_noise* noise) {
   }
   switch (r->path) {
     case Path::FullRank:
+    case Path::LowRank:
     case Path::Materialised:
       VB_TRY(advance_materialised(c, r, n_steps, nz));
       break;
@@ -1991,7 +2027,8 @@ int vb_log_weights_rows(vb_ctx* c, const vb_family* fam, const vb_target* tgt,
   VB_TRY(check_target(tgt, fi.D));
   if (!lam || !noise || !lw_out || m < 0 || rows < 0) return fail(VB_EINVAL, "null argument");
   if (rows > 65535) return fail(VB_EINVAL, "rows must be <= 65535");
-  if (vbk::family_full_rank(fi.kind)) return fail(VB_EUNSUPPORTED, "rows of log weights: mean-field families only");
+  if (vbk::family_full_rank(fi.kind) || fi.kind == VB_FAMILY_LR_GAUSSIAN)
+    return fail(VB_EUNSUPPORTED, "rows of log weights: mean-field families only");
   if (noise->kind != VB_NOISE_PHILOX) return fail(VB_EINVAL, "rows of log weights need Philox noise");
   // (a pairing choose_path rejects has no rows kernel either)
   Path path;
@@ -2020,7 +2057,7 @@ int vb_log_weights(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const 
   if (!lam || !noise || !lw_out || m < 0) return fail(VB_EINVAL, "null argument");
   Path path;
   VB_TRY(choose_path({fi.kind, tgt->kind, fi.D}, &path));
-  const bool fr = path == Path::FullRank;
+  const bool fr = family_path(path);
   const bool host = noise->kind == VB_NOISE_HOST;
   if (host && !noise->eps) return fail(VB_EINVAL, "host noise requires eps");
   // (the fused kernels' launch function takes m == 0 itself)
@@ -2030,7 +2067,8 @@ int vb_log_weights(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const 
   VB_TRY(dl.stage(c, 0, lam, fi.P));
   // full-rank t: each draw carries its scale s beside z
   const bool frg = fr && fi.kind == VB_FAMILY_FR_GAUSSIAN;
-  if (host) VB_TRY(dn.stage(c, 1, noise->eps, (size_t)m * fi.D + (fr && !frg ? m : 0)));
+  if (host)
+    VB_TRY(dn.stage(c, 1, noise->eps, (size_t)m * (fr ? vbk::family_noise_width(fi) : (size_t)fi.D)));
   VB_TRY(dlw.stage(c, 2, lw_out, (size_t)m));
   VB_TRY(dxs.stage(c, 3, samples_out, samples_out ? (size_t)m * fi.D : 0));
   const vbk::Noise nz = noise_of(noise, host ? dn.d : nullptr);
@@ -2044,7 +2082,9 @@ int vb_log_weights(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const 
     vbk::FrWork* W;
     VB_TRY(fr_work(c, &W));
     const vbk::Spec f = make_spec(fi, tgt, nullptr, tp, tc, heads);
-    if (frg)
+    if (path == Path::LowRank)
+      VB_TRY(vbk::lrg_log_weights(W, f, dl.d, m, nz, dlw.d, dxs.d, c->stream));
+    else if (frg)
       VB_TRY(vbk::frg_log_weights(W, f, dl.d, m, nz, dlw.d, dxs.d, c->stream));
     else if (fr)
       VB_TRY(vbk::fr_log_weights(W, f, dl.d, m, nz, dlw.d, dxs.d, c->stream));

@@ -1451,6 +1451,7 @@ struct FrWork {
   // N x D / N
   Buf Z, X, G, s, logp, zz, r, rk;
   Buf glm;  // regression / multilevel target: chunk partials (glm_target_eval, mlm_target_eval)
+  Buf lrg;  // the low-rank Gaussian family's own workspace (fr_extra, vb_lrg.hip)
   // pinned host staging for host-callback targets
   double *hx = nullptr, *hlp = nullptr, *hg = nullptr;
   size_t hcap = 0;
@@ -1613,6 +1614,13 @@ int fr_rows(FrWork* W, int D, long long n, FrRows* out) {
   if (int rc = reserve_n(W, D, n)) return rc;
   FR_HIP(W->scal.reserve(sizeof(double) * 8));
   *out = FrRows{W->Z.d(), W->X.d(), W->G.d(), W->logp.d(), W->zz.d(), W->scal.d()};
+  return 0;
+}
+
+// Workspace of the low-rank Gaussian family (vb_lrg.hip)
+int fr_extra(FrWork* W, size_t doubles, double** out) {
+  FR_HIP(W->lrg.reserve(sizeof(double) * std::max<size_t>(doubles, 1)));
+  *out = W->lrg.d();
   return 0;
 }
 

@@ -17,6 +17,7 @@ struct Family {
   double df;
   double t_scale, shape;  // mf t: sqrt(df/2), df/2
   double t_const;         // log normaliser of the t density (per coordinate / multivariate)
+  int R = 0;              // low-rank Gaussian (kFamilyLrGaussian): columns of B
 };
 
 // Where a launch takes its standardized draws from: host-generated draws already in
@@ -397,6 +398,29 @@ int frg_value_grad(FrWork* W, const Spec& f, const double* lam, const Noise& nz,
 int frg_logdensity(FrWork* W, const Family& f, const double* lam, const double* x, long long n,
                    double* out, hipStream_t st);
 int frg_log_weights(FrWork* W, const Spec& f, const double* lam, long long m, const Noise& nz,
+                    double* lw, double* xs, hipStream_t st);
+
+// ---- low-rank-plus-diagonal Gaussian family (vb_lrg.hip) ------------------------
+// lambda = [mu (D), log_d (D), B row-major (D x R)], Sigma = B B^T + diag(exp(2 log_d)).
+constexpr int kFamilyLrGaussian = 4;
+constexpr int kLrgRankMax = 64;
+// Standard normals per draw of a family on the FullRank / LowRank paths: z (D), the
+// t family's scale s (1), the low-rank family's u (R).
+inline size_t family_noise_width(const Family& f) {
+  return (size_t)f.D + (f.kind == kFamilyFrT ? 1 : 0) + (f.kind == kFamilyLrGaussian ? f.R : 0);
+}
+// `doubles` of workspace that only vb_lrg.hip uses (kept across calls, grown on demand)
+int fr_extra(FrWork* W, size_t doubles, double** out);
+// nz.eps (host draws) = [n][D + R] on the device, N(0,1): each row is [z (D), u (R)]
+int lrg_sample(FrWork* W, const Family& f, const double* lam, long long n, const Noise& nz,
+               double* x, hipStream_t st);
+// up (non-null): the windowed adagrad step is fused into the gradient kernel's
+// epilogue (lam updated in place, ring / history row written, grad untouched)
+int lrg_value_grad(FrWork* W, const Spec& f, const double* lam, const Noise& nz, double* value,
+                   double* grad, hipStream_t st, const MfUpdate* up = nullptr);
+int lrg_logdensity(FrWork* W, const Family& f, const double* lam, const double* x, long long n,
+                   double* out, hipStream_t st);
+int lrg_log_weights(FrWork* W, const Spec& f, const double* lam, long long m, const Noise& nz,
                     double* lw, double* xs, hipStream_t st);
 
 }  // namespace vbk

@@ -76,7 +76,7 @@ def _rows_supported(fam, target):
     (vb_capi.hip vb_log_weights_rows: mean-field family, device target,
     separable or D <= 16)."""
     from .targets import Target
-    if fam.kind in nat.FULL_RANK_FAMILIES or not isinstance(target, Target):
+    if fam.kind in nat.CORRELATED_FAMILIES or not isinstance(target, Target):
         return False
     if target.kind in (nat.TARGET_CALLBACK, nat.TARGET_REGRESSION, nat.TARGET_HIERARCHICAL,
                        nat.TARGET_MULTILEVEL):
@@ -139,7 +139,7 @@ def _native_compute(ids, inits, family_factory, target, n_iters, n_samples, n_bo
     khat_fn = lambda: psis.psis_khat(lw.t()) if len(ids) > 1 else np.array([psis.psis_khat(lw[0])])
     # (a full-rank family's moments below call the library: no concurrent calls
     # on the context, so the k-hats run first there)
-    full_rank = bfam.kind in nat.FULL_RANK_FAMILIES
+    full_rank = bfam.kind in nat.CORRELATED_FAMILIES
     use_worker = not full_rank and os.environ.get('VIABEL_AMD_PSIS_WORKER', '0') == '1'
     khat_job = _psis_worker().submit(khat_fn) if use_worker else None
     khat = khat_fn() if (khat_job is None and full_rank) else None

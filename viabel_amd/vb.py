@@ -7,6 +7,7 @@ error messages) for the hot path:
   mean_field_t_variational_family         vb.py:140-182
   t_variational_family (full rank)        vb.py:185-233, _distributions.py:8-38
   cholesky_gaussian_variational_family    what vb.py:85-137 was meant to be
+  low_rank_gaussian_variational_family    Sigma = B B^T + diag(d^2) (not in the reference)
   black_box_klvi                          vb.py:236-245
   black_box_chivi                         vb.py:248-266
   black_box_klvi_pd / black_box_klvi_pd2  vb.py:268-295
@@ -46,6 +47,7 @@ __all__ = [
     'mean_field_t_variational_family',
     'full_rank_gaussian_variational_family',
     'cholesky_gaussian_variational_family',
+    'low_rank_gaussian_variational_family',
     't_variational_family',
     'black_box_klvi',
     'black_box_chivi',
@@ -78,7 +80,8 @@ class NativeVariationalFamily(VariationalFamily):
     """VariationalFamily namedtuple carrying the device descriptor and RNG state."""
 
     def _struct(self):
-        return nat.Family(self.kind, 0, self.dim, float(self.df or 0.0))
+        return nat.Family(self.kind, int(self.__dict__.get('rank', 0)), self.dim,
+                          float(self.df or 0.0))
 
     # the family's own RandomState(0) (vb.py:49 / 143 / 195), made on first use:
     # constructing one costs ~0.25 ms of host time (MT19937 seeding), and a Philox
@@ -99,6 +102,8 @@ class NativeVariationalFamily(VariationalFamily):
         rs = self.rs if seed is None else np.random.RandomState(seed)
         if self.kind in (nat.FAMILY_MF_GAUSSIAN, nat.FAMILY_FR_GAUSSIAN):
             return rs.randn(n, self.dim)                              # vb.py:52 / 105
+        if self.kind == nat.FAMILY_LR_GAUSSIAN:
+            return rs.randn(n, self.dim + self.rank)                  # rows [z (D), u (R)]
         if self.kind == nat.FAMILY_FR_T:
             # vb.py:204-206: chisquare first, then randn; flat [s (n), z (n x D)]
             s = np.sqrt(rs.chisquare(self.df, n) / self.df)
@@ -348,6 +353,89 @@ def cholesky_gaussian_variational_family(dim, rng=None):
 
     fam = NativeVariationalFamily(sample, entropy, logdensity, mean_and_cov, pth_moment, P)
     fam.kind, fam.dim, fam.df, fam.rng = nat.FAMILY_FR_GAUSSIAN, dim, None, rng
+    fam.seed, fam.stream, fam.step = 0, next(_STREAMS) & 0xFFFFFF, 0
+    return fam
+
+
+def low_rank_gaussian_variational_family(dim, rank, rng=None):
+    """Gaussian with covariance Sigma = B B^T + diag(d^2), B [dim][rank]: the rank
+    strongest posterior directions at dim (rank + 2) parameters and O(N dim rank)
+    work per step.  var_param = [mu (dim), log_d (dim), B (dim x rank, row-major)],
+    d = exp(log_d), 1 <= rank <= min(dim, 64).  sample is x = mu + d z + B u on one
+    row [z (dim), u (rank)] of standard normals per draw: randn(n, dim + rank) from
+    the family's RandomState(0) or, with rng='philox', the generator's Gaussian row
+    at width dim + rank.  With W = diag(1/d) B and C = I + W^T W the entropy is
+    D/2 (1 + log 2 pi) + sum log_d + 1/2 log det C."""
+    rng = _DEFAULT_RNG[0] if rng is None else rng
+    if rng not in ('numpy', 'philox'):
+        raise ValueError("rng must be 'numpy' or 'philox'")
+    dim = int(dim)
+    if isinstance(rank, bool) or int(rank) != rank or not 1 <= int(rank) <= min(dim, 64):
+        raise ValueError('rank must be an integer with 1 <= rank <= min(dim, 64)')
+    rank = int(rank)
+    P = dim * (rank + 2)
+
+    def _lam(var_param):
+        lam = nat.as_f64(var_param)
+        if lam.shape != (P,):
+            raise ValueError('var_param must have shape (%d,)' % P)
+        return lam
+
+    def _parts(var_param):
+        lam = _lam(var_param)
+        return lam[:dim], lam[dim:2 * dim], lam[2 * dim:].reshape(dim, rank)
+
+    def sample(var_param, n_samples, seed=None):
+        lam = _lam(var_param)
+        out = np.empty((int(n_samples), dim))
+        if fam.rng == 'numpy':
+            eps = nat.as_f64(fam._draw(int(n_samples), seed))
+            nz = nat.Noise(nat.NOISE_HOST, 0, 0, 0, nat.dptr(eps))
+        else:
+            nz = fam._philox_noise(seed)
+        nat.check(nat.lib().vb_family_sample(nat.context().handle, fam._struct(), nat.dptr(lam),
+                                             int(n_samples), nz, nat.dptr(out)))
+        return out
+
+    def logdensity(x, var_param):
+        lam = _lam(var_param)
+        xx = np.asarray(x, dtype=float)
+        one_d = xx.ndim == 1
+        xx = nat.as_f64(np.atleast_2d(xx))
+        if xx.shape[1] != dim:
+            raise ValueError('x must have %d columns' % dim)
+        out = np.empty(xx.shape[0])
+        nat.check(nat.lib().vb_family_logdensity(nat.context().handle, fam._struct(),
+                                                 nat.dptr(lam), nat.dptr(xx), xx.shape[0],
+                                                 nat.dptr(out)))
+        return out[0] if one_d else out
+
+    def entropy(var_param):
+        _, log_d, B = _parts(var_param)
+        W = B / np.exp(log_d)[:, None]
+        L = np.linalg.cholesky(np.eye(rank) + W.T @ W)
+        return (0.5 * dim * (1.0 + LOG2PI) + np.sum(log_d)) + np.sum(np.log(np.diag(L)))
+
+    def mean_and_cov(var_param):
+        mu, log_d, B = _parts(var_param)
+        return mu.copy(), B @ B.T + np.diag(np.exp(2 * log_d))
+
+    def pth_moment(p, var_param):
+        if p not in [2, 4]:
+            raise ValueError('only p = 2 or 4 supported')
+        _, log_d, B = _parts(var_param)
+        d2 = np.exp(2 * log_d)
+        b2 = np.sum(B ** 2, axis=1)                                  # |b_i|^2
+        tr = np.sum(d2) + np.sum(b2)
+        if p == 2:
+            return tr
+        # |Sigma|_F^2 without the D x D matrix
+        fro = np.sum(d2 ** 2) + 2 * np.sum(d2 * b2) + np.sum((B.T @ B) ** 2)
+        return 2 * fro + tr ** 2
+
+    fam = NativeVariationalFamily(sample, entropy, logdensity, mean_and_cov, pth_moment, P)
+    fam.kind, fam.dim, fam.df, fam.rng = nat.FAMILY_LR_GAUSSIAN, dim, None, rng
+    fam.rank = rank
     fam.seed, fam.stream, fam.step = 0, next(_STREAMS) & 0xFFFFFF, 0
     return fam
 
@@ -620,7 +708,7 @@ def _native_adagrad(n_iters, obj, init_param, window, learning_rate, epsilon,
                     learning_rate_end)
     chunk = max(1000, -(-n_iters // 10))
     if fam.rng != 'philox':
-        per_step = obj.n_samples * (fam.dim + 1)
+        per_step = obj.n_samples * (fam.dim + 1 + fam.__dict__.get('rank', 0))
         chunk = max(1, min(chunk, _HOST_CHUNK_ELEMS // max(per_step, 1)))
     bar = _progress(n_iters)
     done = 0
@@ -784,7 +872,7 @@ def _ia_optimize(opt, n_iters, objective_and_grad, init_param, K, has_log_norm, 
             # draws (family stream / global-RNG CHIVI seeds) follow seed(o)
             run = DeviceRun(obj, n_iters, inits[o][None, :], window, learning_rate, epsilon,
                             learning_rate_end, optimizer=opt)
-            per_step = obj.n_samples * (fam.dim + 1)
+            per_step = obj.n_samples * (fam.dim + 1 + fam.__dict__.get('rank', 0))
             chunk = max(1, min(n_iters, _HOST_CHUNK_ELEMS // max(per_step, 1)))
             done = 0
             while done < n_iters:
