@@ -280,7 +280,11 @@ void* vb_ctx_stream(vb_ctx* ctx);
 /* x_out[n, d] = sample of q(lambda); n = 0..n-1.  Noise as above (one problem). */
 int vb_family_sample(vb_ctx* ctx, const vb_family* fam, const double* lam,
                      int64_t n, const vb_noise* noise, double* x_out);
-/* out[n] = log q(x[n, :]; lambda) with all normalising constants. */
+/* out[n] = log q(x[n, :]; lambda) with all normalising constants.  Mean-field t
+ * family: finite up to |z| = |x - mu| / sigma = 1e300 (above 2^500 the term
+ * log1p(z^2 / df) is formed as 2 log|z| - log df + log1p(df / z^2)); vb_log_weights
+ * with host noise alike.  The estimators' step kernels form z * z from the
+ * standardised draw itself: their domain is |eps| < 1.3e154. */
 int vb_family_logdensity(vb_ctx* ctx, const vb_family* fam, const double* lam,
                          const double* x, int64_t n, double* out);
 /* Full-rank family only: sigma_out [D][D] = Sigma = L L^T and eig_out [D] =

@@ -64,7 +64,16 @@ class Family:
             return np.sum(-0.5 * z * z - ls - 0.5 * LOG2PI, axis=1)
         df = self.df
         c = math.lgamma(0.5 * (df + 1)) - math.lgamma(0.5 * df) - 0.5 * np.log(df * np.pi)
-        return np.sum(c - 0.5 * (df + 1) * np.log1p(z * z / df) - ls, axis=1)
+        # z * z overflows from |z| ~ 1.3e154 on while log1p(z^2 / df) ~ 2 log|z| stays
+        # small: above 2^500 the term is 2 log|z| - log df + log1p(df / z^2)
+        # (tests/test_oracle_mf_mp.py; the device's family kernels switch alike)
+        az = np.abs(z)
+        big = az > 2.0 ** 500
+        ab = np.where(big, az, 1.0)
+        zs = np.where(big, 0.0, z)
+        l1 = np.where(big, 2.0 * np.log(ab) - np.log(df) + np.log1p(df / ab / ab),
+                      np.log1p(zs * zs / df))
+        return np.sum(c - 0.5 * (df + 1) * l1 - ls, axis=1)
 
     def mean_and_cov(self, lam):
         mu, ls = self.split(lam)

@@ -8,7 +8,7 @@ cd "$(dirname "$0")/../viabel_amd/csrc"
 mkdir -p build/var_$name
 hash=$(make -s print-hash)
 objs=""
-for f in vb_mf vb_fr vb_rhat vb_bounds vb_psis vb_probe vb_capi; do
+for f in vb_mf vb_fr vb_frg vb_lrg vb_rhat vb_bounds vb_psis vb_probe vb_glm vb_hier vb_mlm vb_capi; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $flags \
     "-DVB_SRC_HASH=\"$hash\"" -c $f.hip -o build/var_$name/$f.o &
   objs="$objs build/var_$name/$f.o"

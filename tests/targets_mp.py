@@ -102,73 +102,99 @@ def _separable(one, x):
     return Ref(lp_hi, lp_lo, lp_S, g_hi[inv], g_lo[inv], g_S[inv])
 
 
-def _funnel(x):
-    n, D = x.shape
+def _funnel_row(xs):
+    """One funnel row at multiprecision coordinates xs: (lp, S_lp, [g_d], [S_d])."""
+    D = len(xs)
     s0 = mpf('1.35')
     half_l2pi = mp.log(2 * mp.pi) / 2
+    v = xs[1]
+    zv = v / s0
+    lp = -zv * zv / 2 - mp.log(s0) - half_l2pi
+    s_lp = zv * zv / 2 + abs(mp.log(s0)) + half_l2pi
+    gv = -v / s0 ** 2
+    s_gv = abs(gv)
+    inv_s2 = mp.exp(-2 * v)
+    g, gS = [None] * D, [None] * D
+    for d in range(D):
+        if d == 1:
+            continue
+        xd = xs[d]
+        z2 = xd * xd * inv_s2
+        lp += -z2 / 2 - v - half_l2pi
+        s_lp += z2 / 2 + abs(v) + half_l2pi
+        gv += z2 - 1
+        s_gv += z2 + 1
+        g[d] = -xd * inv_s2
+        gS[d] = abs(g[d])
+    g[1], gS[1] = gv, s_gv
+    return lp, s_lp, g, gS
+
+
+def _es_row(xs):
+    """One eight-schools row at multiprecision coordinates xs, as _funnel_row."""
+    assert len(xs) == 10
+    mu, u = xs[0], xs[1]
+    tau = mp.exp(u)
+    w = (tau / 5) ** 2
+    l1 = mp.log1p(w)
+    lp = -(mu / 5) ** 2 / 2 - l1 + u
+    s_lp = (mu / 5) ** 2 / 2 + l1 + abs(u)
+    gmu = -mu / 25
+    s_gmu = abs(gmu)
+    gu = -2 * w / (1 + w) + 1
+    s_gu = 2 * w / (1 + w) + 1
+    g, gS = [None] * 10, [None] * 10
+    for j in range(8):
+        th = xs[2 + j]
+        sg = mpf(ES_SIGMA[j])
+        res = (ES_Y[j] - mu - tau * th) / sg
+        lp += -th * th / 2 - res * res / 2
+        s_lp += th * th / 2 + res * res / 2
+        gmu += res / sg
+        s_gmu += abs(res / sg)
+        gu += res * tau * th / sg
+        s_gu += abs(res * tau * th / sg)
+        g[2 + j] = -th + res * tau / sg
+        gS[2 + j] = abs(th) + abs(res * tau / sg)
+    g[0], gS[0], g[1], gS[1] = gmu, s_gmu, gu, s_gu
+    return lp, s_lp, g, gS
+
+
+def _sep_row(one):
+    def row(xs):
+        vals = [one(x) for x in xs]
+        return (mp.fsum(v[0] for v in vals), mp.fsum(v[1] for v in vals),
+                [v[2] for v in vals], [v[3] for v in vals])
+    return row
+
+
+def _rows(row, x, D_fixed=None):
+    n, D = x.shape
+    assert D_fixed is None or D == D_fixed
     out = Ref(*(np.empty(n) for _ in range(3)), *(np.empty((n, D)) for _ in range(3)))
     for r in range(n):
-        v = mpf(float(x[r, 1]))
-        zv = v / s0
-        lp = -zv * zv / 2 - mp.log(s0) - half_l2pi
-        s_lp = zv * zv / 2 + abs(mp.log(s0)) + half_l2pi
-        gv = -v / s0 ** 2
-        s_gv = abs(gv)
-        inv_s2 = mp.exp(-2 * v)
-        for d in range(D):
-            if d == 1:
-                continue
-            xd = mpf(float(x[r, d]))
-            z2 = xd * xd * inv_s2
-            lp += -z2 / 2 - v - half_l2pi
-            s_lp += z2 / 2 + abs(v) + half_l2pi
-            gv += z2 - 1
-            s_gv += z2 + 1
-            g = -xd * inv_s2
-            out.g_hi[r, d], out.g_lo[r, d] = _split(g)
-            out.g_S[r, d] = abs(out.g_hi[r, d])
+        lp, s_lp, g, gS = row([mpf(float(v)) for v in x[r]])
         out.lp_hi[r], out.lp_lo[r] = _split(lp)
         out.lp_S[r] = float(s_lp)
-        out.g_hi[r, 1], out.g_lo[r, 1] = _split(gv)
-        out.g_S[r, 1] = float(s_gv)
+        for d in range(D):
+            out.g_hi[r, d], out.g_lo[r, d] = _split(g[d])
+            # a gradient entry that is one product carries S = |the rounded entry|
+            out.g_S[r, d] = abs(out.g_hi[r, d]) if gS[d] == abs(g[d]) else float(gS[d])
     return out
+
+
+def _funnel(x):
+    return _rows(_funnel_row, x)
 
 
 def _eight_schools(x):
-    n, D = x.shape
-    assert D == 10
-    out = Ref(*(np.empty(n) for _ in range(3)), *(np.empty((n, D)) for _ in range(3)))
-    for r in range(n):
-        mu, u = mpf(float(x[r, 0])), mpf(float(x[r, 1]))
-        tau = mp.exp(u)
-        w = (tau / 5) ** 2
-        l1 = mp.log1p(w)
-        lp = -(mu / 5) ** 2 / 2 - l1 + u
-        s_lp = (mu / 5) ** 2 / 2 + l1 + abs(u)
-        gmu = -mu / 25
-        s_gmu = abs(gmu)
-        gu = -2 * w / (1 + w) + 1
-        s_gu = 2 * w / (1 + w) + 1
-        for j in range(8):
-            th = mpf(float(x[r, 2 + j]))
-            sg = mpf(ES_SIGMA[j])
-            res = (ES_Y[j] - mu - tau * th) / sg
-            lp += -th * th / 2 - res * res / 2
-            s_lp += th * th / 2 + res * res / 2
-            gmu += res / sg
-            s_gmu += abs(res / sg)
-            gu += res * tau * th / sg
-            s_gu += abs(res * tau * th / sg)
-            g = -th + res * tau / sg
-            out.g_hi[r, 2 + j], out.g_lo[r, 2 + j] = _split(g)
-            out.g_S[r, 2 + j] = float(abs(th) + abs(res * tau / sg))
-        out.lp_hi[r], out.lp_lo[r] = _split(lp)
-        out.lp_S[r] = float(s_lp)
-        out.g_hi[r, 0], out.g_lo[r, 0] = _split(gmu)
-        out.g_S[r, 0] = float(s_gmu)
-        out.g_hi[r, 1], out.g_lo[r, 1] = _split(gu)
-        out.g_S[r, 1] = float(s_gu)
-    return out
+    return _rows(_es_row, x, 10)
+
+
+# one row at multiprecision coordinates (a list of mpf, inside mp.workdps(DIGITS)):
+# (lp, S_lp, [g_d], [S_d]) -- for references whose x is itself a multiprecision result
+ROW = {'isogauss': _sep_row(_iso1), 'mixture': _sep_row(_mix1), 'funnel': _funnel_row,
+       'eight_schools_ncp': _es_row}
 
 
 _EVAL = {'isogauss': lambda x: _separable(_iso1, x), 'mixture': lambda x: _separable(_mix1, x),

@@ -1163,7 +1163,9 @@ __global__ __launch_bounds__(HOST ? (SPLIT ? 320 : 256) : kBlockMaxThreads) void
           for (int k = 0; k <= 2 * DMAX; ++k) acc[k] *= f;
           mloc = lw;
         }
-        const double wgt = exp_fast(a.alpha * (lw - mloc));
+        // lw = -inf while this thread's max is still -inf (its first samples
+        // overflowed): -inf - -inf is NaN, the weight is 0 (a NaN lw stays NaN)
+        const double wgt = lw == -INFINITY ? 0.0 : exp_fast(a.alpha * (lw - mloc));
 #pragma unroll
         for (int d = 0; d < DMAX; ++d) {
           acc[d] += wgt * g[d];
@@ -1219,7 +1221,9 @@ __global__ __launch_bounds__(HOST ? (SPLIT ? 320 : 256) : kBlockMaxThreads) void
           for (int k = 0; k < KH; ++k) acch[k] *= f;
           mloc = lw;
         }
-        const double wgt = exp_fast(a.alpha * (lw - mloc));
+        // lw = -inf while this thread's max is still -inf (its first samples
+        // overflowed): -inf - -inf is NaN, the weight is 0 (a NaN lw stays NaN)
+        const double wgt = lw == -INFINITY ? 0.0 : exp_fast(a.alpha * (lw - mloc));
 #pragma unroll
         for (int k = 0; k < DH; ++k) {
           acch[k] += wgt * gh[k];
@@ -2017,6 +2021,17 @@ __global__ __launch_bounds__(256) void sample_kernel(int D, long long n, const d
   if (dB < D) x[r * D + dB] = eB * exp(lam[D + dB]) + lam[dB];
 }
 
+// log1p(z^2 / df) of the t family's log q, off the step kernels' chain (the family's
+// logdensity kernels and the log-weight kernels' host-noise form): z * z overflows
+// from |z| ~ 1.3e154 on while the term itself stays ~ 2 log|z|.  Above |z| = 2^500
+// it is written 2 log|z| - log df + log1p(df / z^2); below, the plain form (the
+// same bits as before).  Finite up to the largest finite |z|.
+__device__ __forceinline__ double log1p_z2_df(double z, double df) {
+  const double az = fabs(z);
+  if (az > 0x1p500) return 2.0 * log(az) - log(df) + log1p(df / az / az);
+  return log1p(z * z / df);
+}
+
 // one wavefront per row: out[r] = sum_d log q_d(x[r, d])
 template <bool TFAM>
 __global__ __launch_bounds__(256) void family_logdensity_kernel(int D, long long n,
@@ -2031,7 +2046,7 @@ __global__ __launch_bounds__(256) void family_logdensity_kernel(int D, long long
     const double ls = lam[D + d];
     const double z = (x[r * D + d] - lam[d]) / exp(ls);
     if constexpr (TFAM)
-      acc += t_const - log1p(z * z / df) * (0.5 * (df + 1.0)) - ls;
+      acc += t_const - log1p_z2_df(z, df) * (0.5 * (df + 1.0)) - ls;
     else
       acc += -0.5 * z * z - ls - 0.5 * kLog2Pi;
   }
@@ -2112,7 +2127,7 @@ __global__ __launch_bounds__(1024) void family_logdensity_rowblock_kernel(int D,
     const double ls = lam[D + d];
     const double z = (x[r * D + d] - lam[d]) / exp(ls);
     if constexpr (TFAM)
-      acc += t_const - log1p(z * z / df) * (0.5 * (df + 1.0)) - ls;
+      acc += t_const - log1p_z2_df(z, df) * (0.5 * (df + 1.0)) - ls;
     else
       acc += -0.5 * z * z - ls - 0.5 * kLog2Pi;
   }
@@ -2255,10 +2270,9 @@ __device__ __forceinline__ double logq1s(double x, double mu, double ls, double 
                                          double t_const, const double2* lt) {
   const double z = (x - mu) / sg;
   if constexpr (TFAM) {
-    const double y = z * z / df;
     double l1;
-    if constexpr (HOST) l1 = log1p(y);
-    else l1 = log1p_pos_tab(y, lt);
+    if constexpr (HOST) l1 = log1p_z2_df(z, df);
+    else l1 = log1p_pos_tab(z * z / df, lt);
     return t_const - l1 * (0.5 * (df + 1.0)) - ls;
   }
   return -0.5 * z * z - ls - 0.5 * kLog2Pi;
@@ -2269,10 +2283,9 @@ __device__ __forceinline__ double logq1(double x, double mu, double ls, double d
                                         double t_const, const double2* lt) {
   const double z = (x - mu) / exp(ls);
   if constexpr (TFAM) {
-    const double y = z * z / df;
     double l1;
-    if constexpr (HOST) l1 = log1p(y);
-    else l1 = log1p_pos_tab(y, lt);
+    if constexpr (HOST) l1 = log1p_z2_df(z, df);
+    else l1 = log1p_pos_tab(z * z / df, lt);
     return t_const - l1 * (0.5 * (df + 1.0)) - ls;
   }
   return -0.5 * z * z - ls - 0.5 * kLog2Pi;
