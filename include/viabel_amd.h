@@ -110,16 +110,30 @@ enum vb_target_kind {
  *   gaussian         l = log N(y; eta, sigma^2)
  *   student_t        l = log t_nu(y; eta, sigma)
  *   bernoulli_logit  l = y eta - softplus(eta)
+ * and the two count likelihoods, log-linear in the mean with a known per-observation
+ * offset, eta_m = x_m . beta + eta0_m (eta0 = log exposure):
+ *   poisson_log         y ~ Poisson(e^eta):  l = y eta - exp(eta) + c_m,
+ *                       c_m = -lgamma(y + 1); -inf where exp(eta) overflows
+ *   neg_binomial_2_log  mean mu = e^eta, variance mu + mu^2 / phi, phi > 0 fixed; with
+ *                       zeta = eta - log phi:  l = y eta - (y + phi) softplus(zeta) + c_m,
+ *                       c_m = lgamma(y + phi) - lgamma(phi) - y log phi - lgamma(y + 1)
+ * The library adds c_data = sum_m c_m as the caller gives it.
  * vb_target.params (host or device memory; dim = D):
- *   params[0] likelihood: 0 gaussian, 1 student_t, 2 bernoulli_logit
+ *   params[0] likelihood: 0 gaussian, 1 student_t, 2 bernoulli_logit, 3 poisson_log,
+ *             4 neg_binomial_2_log
  *   params[1] M (number of observations, >= 1, integral)
- *   params[2] nu   (student_t degrees of freedom, > 0; ignored otherwise)
- *   params[3] sigma (gaussian / student_t scale, > 0; ignored for bernoulli_logit)
+ *   params[2] nu   (student_t degrees of freedom, > 0), or phi (neg_binomial_2_log
+ *             dispersion, > 0); ignored otherwise
+ *   params[3] sigma (gaussian / student_t scale, > 0; ignored for the other likelihoods)
  *   params[4] prior_scale s (> 0): beta_d ~ N(0, s^2) independently
  *   params[5..7] reserved, zero
  *   params[8 ..]          X, row-major [M][D]
- *   params[8 + M*D ..]    y [M]   (bernoulli_logit: 0 or 1)
+ *   params[8 + M*D ..]    y [M]   (bernoulli_logit: 0 or 1; counts: integers >= 0)
  *   n_params = 8 + M*D + M
+ * likelihoods 3 and 4 only, appended (every offset above stays put):
+ *   params[8 + M*D + M ..]   eta0 [M]
+ *   params[8 + M*D + 2 M]    c_data
+ *   n_params = 8 + M*D + M + M + 1
  * vb_run_create copies the block once into the run; one-shot calls stage a host
  * block per call and read a device block in place. */
 
@@ -151,10 +165,12 @@ enum vb_target_kind {
  *   eta_m = x_m . beta + a_g(m); y_m | eta_m through the likelihoods of
  *   VB_TARGET_REGRESSION
  * vb_target.params (host or device memory):
- *   params[0] likelihood: 0 gaussian, 1 student_t, 2 bernoulli_logit
+ *   params[0] likelihood: 0 gaussian, 1 student_t, 2 bernoulli_logit, 3 poisson_log,
+ *             4 neg_binomial_2_log (eta_m = x_m . beta + a_g(m) + eta0_m for 3 and 4)
  *   params[1] M (number of observations, >= 1, integral)
- *   params[2] nu   (student_t degrees of freedom, > 0; ignored otherwise)
- *   params[3] sigma (gaussian / student_t scale, > 0; ignored for bernoulli_logit)
+ *   params[2] nu   (student_t degrees of freedom, > 0), or phi (neg_binomial_2_log
+ *             dispersion, > 0); ignored otherwise
+ *   params[3] sigma (gaussian / student_t scale, > 0; ignored for the other likelihoods)
  *   params[4] prior_scale s (> 0)
  *   params[5] G (number of groups, >= 1, integral)
  *   params[6] s_tau (> 0)
@@ -165,6 +181,10 @@ enum vb_target_kind {
  *                               off[g] <= m < off[g + 1]; exact integers, off[0] = 0,
  *                               off[G] = M, non-decreasing (an empty group has its prior only)
  *   n_params = 8 + M*p + M + G + 1
+ * likelihoods 3 and 4 only, appended (every offset above stays put):
+ *   params[8 + M*p + M + G + 1 ..]    eta0 [M], in the observations' sorted order
+ *   params[8 + M*p + 2 M + G + 1]     c_data
+ *   n_params = 8 + M*p + M + (G + 1) + M + 1
  * Staged and copied as the regression block is. */
 
 /* User target: log p and d log p / dx of the n rows of x [n][d] (HOST memory,

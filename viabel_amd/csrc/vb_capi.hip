@@ -579,29 +579,44 @@ int regression_head(const vb_target* t, vbk::GlmHead* o) {
     VB_HIP(hipMemcpy(h, t->params, sizeof h, hipMemcpyDeviceToHost));
   else
     std::memcpy(h, t->params, sizeof h);
-  if (!(h[0] == 0.0 || h[0] == 1.0 || h[0] == 2.0))
-    return fail(VB_EINVAL, "regression target: params[0] (likelihood) must be 0, 1 or 2, got %g", h[0]);
+  if (!(h[0] == 0.0 || h[0] == 1.0 || h[0] == 2.0 || h[0] == 3.0 || h[0] == 4.0))
+    return fail(VB_EINVAL, "regression target: params[0] (likelihood) must be 0, 1, 2, 3 or 4, got %g", h[0]);
   if (!(h[1] >= 1.0 && h[1] <= 9.0e15 && h[1] == std::floor(h[1])))
     return fail(VB_EINVAL, "regression target: params[1] (M) must be an integer >= 1, got %g", h[1]);
   const int lik = (int)h[0];
   if (lik == 1 && !(h[2] > 0.0 && std::isfinite(h[2])))
     return fail(VB_EINVAL, "regression target: params[2] (nu) must be positive, got %g", h[2]);
-  if (lik != 2 && !(h[3] > 0.0 && std::isfinite(h[3])))
+  if (lik == 4 && !(h[2] > 0.0 && std::isfinite(h[2])))
+    return fail(VB_EINVAL, "regression target: params[2] (phi) must be positive, got %g", h[2]);
+  if (lik < 2 && !(h[3] > 0.0 && std::isfinite(h[3])))
     return fail(VB_EINVAL, "regression target: params[3] (sigma) must be positive, got %g", h[3]);
   if (!(h[4] > 0.0 && std::isfinite(h[4])))
     return fail(VB_EINVAL, "regression target: params[4] (prior_scale) must be positive, got %g", h[4]);
   for (int i = 5; i < vbk::kGlmHeader; ++i)
     if (h[i] != 0.0)
       return fail(VB_EINVAL, "regression target: params[%d] (reserved) must be zero, got %g", i, h[i]);
-  const double want = (double)vbk::kGlmHeader + h[1] * (double)t->dim + h[1];
+  const bool count = lik >= 3;   // eta0 [M] and c_data follow y
+  const double want =
+      (double)vbk::kGlmHeader + h[1] * (double)t->dim + h[1] + (count ? h[1] + 1.0 : 0.0);
   if ((double)t->n_params != want)
-    return fail(VB_EINVAL, "regression target: n_params %lld does not match 8 + M*D + M = %.0f (M %.0f, dim %lld)",
-                (long long)t->n_params, want, h[1], (long long)t->dim);
+    return fail(VB_EINVAL, "regression target: n_params %lld does not match 8 + M*D + M%s = %.0f (M %.0f, dim %lld)",
+                (long long)t->n_params, count ? " + M + 1" : "", want, h[1], (long long)t->dim);
   o->lik = lik;
   o->M = (long long)h[1];
   o->nu = h[2];
   o->sigma = h[3];
   o->prior = h[4];
+  o->phi = lik == 4 ? h[2] : 0.0;
+  o->c_data = 0.0;
+  if (count) {
+    const double* cp = t->params + (size_t)t->n_params - 1;
+    if (pc == 1)
+      VB_HIP(hipMemcpy(&o->c_data, cp, sizeof(double), hipMemcpyDeviceToHost));
+    else
+      o->c_data = *cp;
+    if (!std::isfinite(o->c_data))
+      return fail(VB_EINVAL, "regression target: the last value (c_data) must be finite, got %g", o->c_data);
+  }
   return VB_OK;
 }
 
@@ -657,14 +672,16 @@ int multilevel_head(const vb_target* t, vbk::MlmHead* o) {
     VB_HIP(hipMemcpy(h, t->params, sizeof h, hipMemcpyDeviceToHost));
   else
     std::memcpy(h, t->params, sizeof h);
-  if (!(h[0] == 0.0 || h[0] == 1.0 || h[0] == 2.0))
-    return fail(VB_EINVAL, "multilevel target: params[0] (likelihood) must be 0, 1 or 2, got %g", h[0]);
+  if (!(h[0] == 0.0 || h[0] == 1.0 || h[0] == 2.0 || h[0] == 3.0 || h[0] == 4.0))
+    return fail(VB_EINVAL, "multilevel target: params[0] (likelihood) must be 0, 1, 2, 3 or 4, got %g", h[0]);
   if (!(h[1] >= 1.0 && h[1] <= 9.0e15 && h[1] == std::floor(h[1])))
     return fail(VB_EINVAL, "multilevel target: params[1] (M) must be an integer >= 1, got %g", h[1]);
   const int lik = (int)h[0];
   if (lik == 1 && !(h[2] > 0.0 && std::isfinite(h[2])))
     return fail(VB_EINVAL, "multilevel target: params[2] (nu) must be positive, got %g", h[2]);
-  if (lik != 2 && !(h[3] > 0.0 && std::isfinite(h[3])))
+  if (lik == 4 && !(h[2] > 0.0 && std::isfinite(h[2])))
+    return fail(VB_EINVAL, "multilevel target: params[2] (phi) must be positive, got %g", h[2]);
+  if (lik < 2 && !(h[3] > 0.0 && std::isfinite(h[3])))
     return fail(VB_EINVAL, "multilevel target: params[3] (sigma) must be positive, got %g", h[3]);
   if (!(h[4] > 0.0 && std::isfinite(h[4])))
     return fail(VB_EINVAL, "multilevel target: params[4] (prior_scale) must be positive, got %g", h[4]);
@@ -678,14 +695,16 @@ int multilevel_head(const vb_target* t, vbk::MlmHead* o) {
   if (!(p >= 1.0))
     return fail(VB_EINVAL, "multilevel target: dim %lld does not leave p >= 1 beside 1 + G = %.0f",
                 (long long)t->dim, 1.0 + h[5]);
-  const double want = (double)vbk::kMlmHeader + h[1] * p + h[1] + h[5] + 1.0;
+  const bool count = lik >= 3;   // eta0 [M] and c_data follow the group offsets
+  const double tail = count ? h[1] + 1.0 : 0.0;
+  const double want = (double)vbk::kMlmHeader + h[1] * p + h[1] + h[5] + 1.0 + tail;
   if ((double)t->n_params != want)
     return fail(VB_EINVAL,
-                "multilevel target: n_params %lld does not match 8 + M*p + M + G + 1 = %.0f (M %.0f, "
-                "p %.0f, G %.0f)", (long long)t->n_params, want, h[1], p, h[5]);
+                "multilevel target: n_params %lld does not match 8 + M*p + M + G + 1%s = %.0f (M %.0f, "
+                "p %.0f, G %.0f)", (long long)t->n_params, count ? " + M + 1" : "", want, h[1], p, h[5]);
   // the group offsets: exact integers, 0 first, M last, non-decreasing
   const size_t ng = (size_t)h[5] + 1;
-  const double* offp = t->params + (size_t)(want - (double)ng);
+  const double* offp = t->params + (size_t)(want - tail - (double)ng);
   std::vector<double> off(ng);
   if (pc == 1)
     VB_HIP(hipMemcpy(off.data(), offp, sizeof(double) * ng, hipMemcpyDeviceToHost));
@@ -709,6 +728,17 @@ int multilevel_head(const vb_target* t, vbk::MlmHead* o) {
   o->sigma = h[3];
   o->prior = h[4];
   o->tau_scale = h[6];
+  o->phi = lik == 4 ? h[2] : 0.0;
+  o->c_data = 0.0;
+  if (count) {
+    const double* cp = t->params + (size_t)t->n_params - 1;
+    if (pc == 1)
+      VB_HIP(hipMemcpy(&o->c_data, cp, sizeof(double), hipMemcpyDeviceToHost));
+    else
+      o->c_data = *cp;
+    if (!std::isfinite(o->c_data))
+      return fail(VB_EINVAL, "multilevel target: the last value (c_data) must be finite, got %g", o->c_data);
+  }
   return VB_OK;
 }
 

@@ -3,8 +3,9 @@
 // log p(beta) = sum_d log N(beta_d; 0, s^2) + sum_m l(y_m, x_m . beta) and its
 // gradient -beta / s^2 + sum_m l'(y_m, eta_m) x_m for the n sample rows beta of
 // x [n][D], over the data matrix X [M][D] and responses y [M] of the target's
-// parameter block (layout in include/viabel_amd.h), with the gaussian, student_t
-// and bernoulli_logit links.  All arithmetic is fp64.
+// parameter block (layout in include/viabel_amd.h), with the gaussian, student_t,
+// bernoulli_logit, poisson_log and neg_binomial_2_log links; the two count links add
+// the block's per-observation offset eta0 [M] to eta.  All arithmetic is fp64.
 //
 // The grid is sample-row tiles x observation chunks (x column slabs on the matrix
 // path): a fit step has ~100 rows, so the observations must fill the chip.  Each
@@ -54,6 +55,7 @@ struct GlmK {
   double* grad;            // [n][D] or null
   double* plp;             // [nchunk][n]      (nchunk > 1)
   double* pg;              // [nchunk][n][D]   (nchunk > 1, grad)
+  const double* eta0;      // [M]: offset of eta (LIK >= 3; not read otherwise)
 };
 
 // l(y, eta) without its constant, and dl / d eta
@@ -69,11 +71,22 @@ __device__ __forceinline__ void glm_link(const GlmK& k, double eta, double y, do
     const double r2 = r * r;
     l = -k.k1 * log1p(r2 * k.k0);
     dl = k.k2 * r / (k.k3 + r2);
-  } else {                           // bernoulli_logit: softplus and the logistic from one exp
+  } else if constexpr (LIK == 2) {   // bernoulli_logit: softplus and the logistic from one exp
     const double e = exp(-fabs(eta));
     l = y * eta - (fmax(eta, 0.0) + log1p(e));
     const double inv = 1.0 / (1.0 + e);
     dl = y - (eta >= 0.0 ? inv : e * inv);
+  } else if constexpr (LIK == 3) {   // poisson_log: -inf past exp's range, no clamp
+    const double e = exp(eta);
+    l = y * eta - e;
+    dl = y - e;
+  } else {                           // neg_binomial_2_log: k0 = phi, k1 = log phi;
+    const double z = eta - k.k1;     // (y + phi) softplus(zeta), zeta = eta - log phi
+    const double e = exp(-fabs(z));
+    const double yp = y + k.k0;
+    l = y * eta - yp * (fmax(z, 0.0) + log1p(e));
+    const double inv = 1.0 / (1.0 + e);
+    dl = y - yp * (z >= 0.0 ? inv : e * inv);
   }
 }
 
@@ -85,7 +98,8 @@ __device__ __forceinline__ double glm_final_logp(const GlmK& k, double sum_l, do
 template <int LIK, bool GRAD, int DP>
 __global__ __launch_bounds__(256) void glm_rows_small_kernel(GlmK k) {
   __shared__ double Xs[kGlmTile * DP];
-  __shared__ double ys[kGlmTile];
+  constexpr bool OFFS = LIK >= 3;               // eta0 rides behind y in the tile
+  __shared__ double ys[OFFS ? 2 * kGlmTile : kGlmTile];
   const int t = threadIdx.x, nt = blockDim.x, D = k.D;
   const long long row = (long long)blockIdx.x * nt + t;
   const bool live = row < k.n;
@@ -106,12 +120,16 @@ __global__ __launch_bounds__(256) void glm_rows_small_kernel(GlmK k) {
       Xs[i] = (mm < cnt && d < D) ? k.X[(mt + mm) * D + d] : 0.0;
     }
     for (int i = t; i < kGlmTile; i += nt) ys[i] = i < cnt ? k.y[mt + i] : 0.0;
+    if constexpr (OFFS) {
+      for (int i = t; i < kGlmTile; i += nt) ys[kGlmTile + i] = i < cnt ? k.eta0[mt + i] : 0.0;
+    }
     __syncthreads();
     for (int mm = 0; mm < cnt; ++mm) {
       const double* xr = Xs + mm * DP;
       double eta = 0.0;
 #pragma unroll
       for (int d = 0; d < DP; ++d) eta = fma(beta[d], xr[d], eta);
+      if constexpr (OFFS) eta += ys[kGlmTile + mm];
       double l, dl;
       glm_link<LIK>(k, eta, ys[mm], l, dl);
       lp += l;
@@ -207,10 +225,15 @@ __global__ __launch_bounds__(256) void glm_rows_mfma_kernel(GlmK k) {
       const d4 eta = e0 + e1;
       const bool ok = mt + lr < m1;
       const double yv = ok ? k.y[mt + lr] : 0.0;
+      double ev = 0.0;
+      if constexpr (LIK >= 3) ev = ok ? k.eta0[mt + lr] : 0.0;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         double l, dl;
-        glm_link<LIK>(k, eta[r], yv, l, dl);
+        if constexpr (LIK >= 3)
+          glm_link<LIK>(k, eta[r] + ev, yv, l, dl);
+        else
+          glm_link<LIK>(k, eta[r], yv, l, dl);
         lpa[r] += ok ? l : 0.0;
         if constexpr (GRAD) Rs[(lq + 4 * r) * kGlmSR + lr] = ok ? dl : 0.0;
       }
@@ -439,11 +462,16 @@ hipError_t launch_glm_rows(int D, long long n, const GlmHead& h, const double* p
     k.k2 = h.nu + 1.0;
     // lgamma((nu + 1) / 2) - lgamma(nu / 2) - log(nu pi) / 2, the log(nu / 2) / 2 cancelled
     c_obs = lgamma_half_step(0.5 * h.nu) - 0.5 * log2pi - std::log(h.sigma);
+  } else if (h.lik == 4) {
+    k.k0 = h.phi;
+    k.k1 = std::log(h.phi);
   }
   k.inv_s2 = 1.0 / (h.prior * h.prior);
   k.c_all = -(double)D * (0.5 * log2pi + std::log(h.prior)) + (double)h.M * c_obs;
+  if (h.lik >= 3) k.c_all += h.c_data;   // the data-only constants, summed by the packer
   k.X = params + kGlmHeader;
   k.y = k.X + (size_t)h.M * D;
+  k.eta0 = h.lik >= 3 ? k.y + h.M : nullptr;
   k.x = x;
   k.logp = logp;
   k.grad = grad;
@@ -453,8 +481,12 @@ hipError_t launch_glm_rows(int D, long long n, const GlmHead& h, const double* p
     glm_launch<0>(p, k, s);
   else if (h.lik == 1)
     glm_launch<1>(p, k, s);
-  else
+  else if (h.lik == 2)
     glm_launch<2>(p, k, s);
+  else if (h.lik == 3)
+    glm_launch<3>(p, k, s);
+  else
+    glm_launch<4>(p, k, s);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || p.nchunk == 1) return e;
   const long long jobs = n + (grad ? n * D : 0);

@@ -217,9 +217,13 @@ constexpr int kTargetRegression = 6;
 // (include/viabel_amd.h); X [M][D] starts kGlmHeader doubles into the block.
 constexpr int kGlmHeader = 8;
 struct GlmHead {
-  int lik;            // 0 gaussian, 1 student_t, 2 bernoulli_logit
+  int lik;            // 0 gaussian, 1 student_t, 2 bernoulli_logit, 3 poisson_log,
+                      // 4 neg_binomial_2_log
   long long M;        // observations
   double nu, sigma, prior;
+  // likelihoods 3 and 4: the dispersion (4), and the block's last value, the sum of the
+  // data-only constants; eta0 [M] follows y in the block
+  double phi, c_data;
 };
 // log p [n] and (grad non-null) d log p / dx [n][D] of the rows of x [n][D] for the
 // regression target whose parameter block is at `params` (device).  scratch holds
@@ -251,10 +255,14 @@ constexpr int kTargetMultilevel = 8;
 // the G + 1 group offsets follow it.
 constexpr int kMlmHeader = 8;
 struct MlmHead {
-  int lik;            // 0 gaussian, 1 student_t, 2 bernoulli_logit
+  int lik;            // 0 gaussian, 1 student_t, 2 bernoulli_logit, 3 poisson_log,
+                      // 4 neg_binomial_2_log
   int centered;       // 0 non-centred, 1 centred
   long long M, G;     // observations, groups; D = p + 1 + G
   double nu, sigma, prior, tau_scale;
+  // likelihoods 3 and 4: the dispersion (4), and the block's last value, the sum of the
+  // data-only constants; eta0 [M] follows the group offsets in the block
+  double phi, c_data;
 };
 // log p [n] and (grad non-null) d log p / dx [n][D] of the rows of x [n][D] for the
 // multilevel target whose parameter block is at `params` (device).  scratch holds

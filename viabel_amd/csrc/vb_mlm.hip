@@ -37,7 +37,8 @@
 //     accumulated in the chunk's partial in global memory (each lane its own row).  No
 //     matrix instructions yet.
 //
-// The links are those of vb_glm.hip's glm_link, operation for operation.
+// The links are those of vb_glm.hip's glm_link, operation for operation; the two count
+// links (poisson_log, neg_binomial_2_log) add the block's offset eta0 [M] to eta.
 // grad == nullptr selects instances without gradient work; the value's operations are
 // the same, so it is the same bit for bit.
 #include <algorithm>
@@ -76,6 +77,7 @@ struct MlmK {
   double* pl;                     // [n][nchunk]: S of its last group, 0 if the same (grad)
   double* psa;                    // [n][nchunk]: sum S_g at_g of the groups inside (grad)
   double* pg;                     // [nchunk][n][p] (grad)
+  const double* eta0;             // [M]: offset of eta (LIK >= 3; not read otherwise)
 };
 
 // l(y, eta) without its constant, and dl / d eta (glm_link of vb_glm.hip)
@@ -91,11 +93,22 @@ __device__ __forceinline__ void mlm_link(const MlmK& k, double eta, double y, do
     const double r2 = r * r;
     l = -k.k1 * log1p(r2 * k.k0);
     dl = k.k2 * r / (k.k3 + r2);
-  } else {                           // bernoulli_logit: softplus and the logistic from one exp
+  } else if constexpr (LIK == 2) {   // bernoulli_logit: softplus and the logistic from one exp
     const double e = exp(-fabs(eta));
     l = y * eta - (fmax(eta, 0.0) + log1p(e));
     const double inv = 1.0 / (1.0 + e);
     dl = y - (eta >= 0.0 ? inv : e * inv);
+  } else if constexpr (LIK == 3) {   // poisson_log: -inf past exp's range, no clamp
+    const double e = exp(eta);
+    l = y * eta - e;
+    dl = y - e;
+  } else {                           // neg_binomial_2_log: k0 = phi, k1 = log phi;
+    const double z = eta - k.k1;     // (y + phi) softplus(zeta), zeta = eta - log phi
+    const double e = exp(-fabs(z));
+    const double yp = y + k.k0;
+    l = y * eta - yp * (fmax(z, 0.0) + log1p(e));
+    const double inv = 1.0 / (1.0 + e);
+    dl = y - yp * (z >= 0.0 ? inv : e * inv);
   }
 }
 
@@ -173,7 +186,8 @@ __device__ __forceinline__ void mlm_store_partials(const MlmK& k, const MlmWalk&
 template <int LIK, bool GRAD, int PP>
 __global__ __launch_bounds__(256) void mlm_rows_lane_kernel(MlmK k) {
   __shared__ double Xs[kMlmTile * PP];
-  __shared__ double ys[kMlmTile];
+  constexpr bool OFFS = LIK >= 3;               // eta0 rides behind y in the tile
+  __shared__ double ys[OFFS ? 2 * kMlmTile : kMlmTile];
   __shared__ int gs[kMlmTile];
   const int t = threadIdx.x, nt = blockDim.x, p = k.p, G = k.G;
   const long long row = (long long)blockIdx.x * nt + t;
@@ -212,6 +226,7 @@ __global__ __launch_bounds__(256) void mlm_rows_lane_kernel(MlmK k) {
     }
     for (int i = t; i < kMlmTile; i += nt) {
       ys[i] = i < cnt ? k.y[mt + i] : 0.0;
+      if constexpr (OFFS) ys[kMlmTile + i] = i < cnt ? k.eta0[mt + i] : 0.0;
       gs[i] = i < cnt ? mlm_group_of(k.off, G, mt + i, gt) : gt;
     }
     __syncthreads();
@@ -221,6 +236,7 @@ __global__ __launch_bounds__(256) void mlm_rows_lane_kernel(MlmK k) {
       double eta = w.aeff;
 #pragma unroll
       for (int d = 0; d < PP; ++d) eta = fma(beta[d], xm[d], eta);
+      if constexpr (OFFS) eta += ys[kMlmTile + mm];
       double l, dl;
       mlm_link<LIK>(k, eta, ys[mm], l, dl);
       lp += l;
@@ -247,7 +263,8 @@ __global__ __launch_bounds__(256) void mlm_rows_lane_kernel(MlmK k) {
 template <int LIK, bool GRAD>
 __global__ __launch_bounds__(64) void mlm_rows_tile_kernel(MlmK k) {
   __shared__ double Xs[kMlmTM * kMlmKS];
-  __shared__ double ys[kMlmTM];
+  constexpr bool OFFS = LIK >= 3;               // eta0 rides behind y
+  __shared__ double ys[OFFS ? 2 * kMlmTM : kMlmTM];
   __shared__ int gs[kMlmTM];
   const int t = threadIdx.x, p = k.p, G = k.G;
   const long long row = (long long)blockIdx.x * 64 + t;
@@ -288,6 +305,7 @@ __global__ __launch_bounds__(64) void mlm_rows_tile_kernel(MlmK k) {
       stage(mt, cnt, c0);
       if (c0 == 0 && t < kMlmTM) {
         ys[t] = t < cnt ? k.y[mt + t] : 0.0;
+        if constexpr (OFFS) ys[kMlmTM + t] = t < cnt ? k.eta0[mt + t] : 0.0;
         gs[t] = t < cnt ? mlm_group_of(k.off, G, mt + t, gt) : gt;
       }
       __syncthreads();
@@ -307,7 +325,10 @@ __global__ __launch_bounds__(64) void mlm_rows_tile_kernel(MlmK k) {
       if (mm < cnt) {
         mlm_enter<GRAD>(k, w, gs[mm], gfirst, glast, tau, it, ar, gr, live);
         double l, dl;
-        mlm_link<LIK>(k, eta[mm] + w.aeff, ys[mm], l, dl);
+        if constexpr (OFFS)
+          mlm_link<LIK>(k, (eta[mm] + w.aeff) + ys[kMlmTM + mm], ys[mm], l, dl);
+        else
+          mlm_link<LIK>(k, eta[mm] + w.aeff, ys[mm], l, dl);
         lp += l;
         if constexpr (GRAD) {
           w.S += dl;
@@ -538,15 +559,20 @@ hipError_t launch_mlm_rows(int D, long long n, const MlmHead& h, const double* p
     k.k2 = h.nu + 1.0;
     // lgamma((nu + 1) / 2) - lgamma(nu / 2) - log(nu pi) / 2, the log(nu / 2) / 2 cancelled
     c_obs = mlm_lgamma_half_step(0.5 * h.nu) - 0.5 * log2pi - std::log(h.sigma);
+  } else if (h.lik == 4) {
+    k.k0 = h.phi;
+    k.k1 = std::log(h.phi);
   }
   k.inv_s2 = 1.0 / (h.prior * h.prior);
   k.inv_stau = 1.0 / h.tau_scale;
   // beta's prior, the observations, the half-Cauchy log(2 / (pi s_tau)), the groups' normal
   k.c_all = -(double)p * (0.5 * log2pi + std::log(h.prior)) + (double)h.M * c_obs +
             (std::log(2.0 / M_PI) - std::log(h.tau_scale)) - (double)h.G * (0.5 * log2pi);
+  if (h.lik >= 3) k.c_all += h.c_data;   // the data-only constants, summed by the packer
   k.X = params + kMlmHeader;
   k.y = k.X + (size_t)h.M * p;
   k.off = k.y + h.M;
+  k.eta0 = h.lik >= 3 ? k.off + h.G + 1 : nullptr;
   k.x = x;
   k.logp = logp;
   k.grad = grad;
@@ -564,8 +590,12 @@ hipError_t launch_mlm_rows(int D, long long n, const MlmHead& h, const double* p
     g ? mlm_launch<0, true>(pl, k, s) : mlm_launch<0, false>(pl, k, s);
   else if (h.lik == 1)
     g ? mlm_launch<1, true>(pl, k, s) : mlm_launch<1, false>(pl, k, s);
-  else
+  else if (h.lik == 2)
     g ? mlm_launch<2, true>(pl, k, s) : mlm_launch<2, false>(pl, k, s);
+  else if (h.lik == 3)
+    g ? mlm_launch<3, true>(pl, k, s) : mlm_launch<3, false>(pl, k, s);
+  else
+    g ? mlm_launch<4, true>(pl, k, s) : mlm_launch<4, false>(pl, k, s);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   if (g)

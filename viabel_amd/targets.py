@@ -20,6 +20,11 @@ Targets:
                          (robust-regression.ipynb; VB_TARGET_REGRESSION)
   robust_regression(x, y, df)   regression with the student_t likelihood
   logistic_regression(x, y)     regression with the bernoulli_logit likelihood
+  poisson_regression(x, y, offset=None)
+                         regression with the poisson_log likelihood: counts y_m with mean
+                         exp(x_m . beta + offset_m), offset = log exposure
+  negative_binomial_regression(x, y, phi, offset=None)
+                         ... with the neg_binomial_2_log likelihood (variance mu + mu^2 / phi)
   hierarchical_normal(y, sigma, centered=False, ...)
                          hierarchical normal means over J groups held on the device,
                          x = [mu, log tau, theta or theta_tilde (J)], D = J + 2, centred
@@ -33,6 +38,9 @@ Targets:
                          non-centred (VB_TARGET_MULTILEVEL)
   multilevel_logistic_regression(x, y, group)     ... with the bernoulli_logit likelihood
   multilevel_robust_regression(x, y, group, df)   ... with the student_t likelihood
+  multilevel_poisson_regression(x, y, group, offset=None)         ... poisson_log
+  multilevel_negative_binomial_regression(x, y, group, phi, offset=None)
+                                                  ... neg_binomial_2_log
 
 User models (the reference's make_stan_log_density, vb.py:314-321, and autograd
 callables): callback(fn, D), from_stan(fit, D) and torch_target(f, D) evaluate
@@ -47,6 +55,8 @@ from . import _native as nat
 
 __all__ = ['Target', 'isogauss', 'mixture', 'funnel', 'eight_schools_ncp', 'corr_gauss',
            'regression', 'robust_regression', 'logistic_regression',
+           'poisson_regression', 'negative_binomial_regression',
+           'multilevel_poisson_regression', 'multilevel_negative_binomial_regression',
            'hierarchical_normal', 'eight_schools_cp',
            'multilevel_regression', 'multilevel_logistic_regression',
            'multilevel_robust_regression',
@@ -135,16 +145,114 @@ def corr_gauss(dim, seed=512):
     return t
 
 
-_LIKELIHOODS = {'gaussian': 0, 'student_t': 1, 'bernoulli_logit': 2}
+_LIKELIHOODS = {'gaussian': 0, 'student_t': 1, 'bernoulli_logit': 2, 'poisson_log': 3,
+                'neg_binomial_2_log': 4}
+_COUNT_LIKELIHOODS = ('poisson_log', 'neg_binomial_2_log')
 REGRESSION_HEADER = 8   # doubles before X in a regression target's parameter block
 
 
-def regression(x, y, likelihood='student_t', df=None, scale=1.0, prior_scale=10.0):
+def count_constant(y, phi=None):
+    """c_data = sum_m c_m, the data-only constants of the count likelihoods:
+      poisson_log         c_m = -lgamma(y_m + 1)
+      neg_binomial_2_log  c_m = lgamma(y_m + phi) - lgamma(phi) - y_m log(phi) - lgamma(y_m + 1)
+    The negative binomial's first three terms are log prod_{j<y} (1 + j / phi) =
+    sum_{j<y} log1p(j / phi): a sum of non-negative terms, taken as it stands up to
+    y = 4096 (the lgamma differences lose it as phi grows: each is ~phi log phi at
+    phi = 1e6).  Above that, Stirling's series for both lgamma with the leading terms
+    cancelled in closed form: with t = y / phi,
+      phi ((1 + t) log1p(t) - t) - log1p(t) / 2 + s(phi + y) - s(phi),
+      s(z) = 1/(12 z) - 1/(360 z^3) + 1/(1260 z^5) - 1/(1680 z^7)
+    (z >= 32: next term below 1e-16; a smaller phi climbs there with y by the
+    product's first factors), (1 + t) log1p(t) - t by its series t^2/2 - t^3/6 + ...
+    below t = 0.1.  Each distinct y is evaluated once and the sum over m is math.fsum."""
+    import math
+    y = np.asarray(y, dtype=np.float64)
+    vals, counts = np.unique(y, return_counts=True)
+
+    def stirling_tail(z):
+        t = 1.0 / z
+        t2 = t * t
+        return t * (1.0 / 12 + t2 * (-1.0 / 360 + t2 * (1.0 / 1260 + t2 * (-1.0 / 1680))))
+
+    def rising(yv):                  # lgamma(y + phi) - lgamma(phi) - y log(phi)
+        if yv <= 4096:
+            return math.fsum(np.log1p(np.arange(int(yv)) / phi).tolist())
+        head, f, k = [], phi, 0
+        while f < 32.0:              # the factors (1 + j / phi) below phi + j = 32
+            head.append(math.log1p(k / phi))
+            f += 1.0
+            k += 1
+        # the rest: prod_{k <= j < y} (1 + j / phi) = Gamma(phi + y) / Gamma(f) / phi^(y - k)
+        n = yv - k
+        t = n / f
+        if t < 0.1:
+            q, tk, i = 0.0, t * t, 2
+            while True:
+                term = tk / (i * (i - 1))
+                q += term if i % 2 == 0 else -term
+                if term <= 1e-20 * abs(q):
+                    break
+                tk *= t
+                i += 1
+        else:
+            q = (1.0 + t) * math.log1p(t) - t
+        body = f * q - 0.5 * math.log1p(t) + (stirling_tail(f + n) - stirling_tail(f))
+        # Gamma(f + n) / Gamma(f) / f^n, then f^n / phi^n
+        return math.fsum(head + [body, n * math.log1p(k / phi)])
+
+    terms = []
+    for v, c in zip(vals.tolist(), counts.tolist()):
+        cm = -math.lgamma(v + 1.0)
+        if phi is not None and v > 0:
+            cm = math.fsum([rising(v), cm])
+        terms += [cm] * c
+    return math.fsum(terms)
+
+
+def _check_counts(likelihood, y, offset, phi, m):
+    """Validation shared by regression and multilevel_regression for the count
+    likelihoods' arguments; returns the offset as a float64 (M,) array (or None)."""
+    count = likelihood in _COUNT_LIKELIHOODS
+    if not count:
+        if offset is not None:
+            raise ValueError('offset is taken by the poisson_log and neg_binomial_2_log '
+                             'likelihoods only, not by %r' % (likelihood,))
+        if phi is not None:
+            raise ValueError('phi is taken by the neg_binomial_2_log likelihood only, not by %r'
+                             % (likelihood,))
+        return None
+    if likelihood == 'neg_binomial_2_log':
+        if phi is None or not (np.isfinite(phi) and phi > 0):
+            raise ValueError('the neg_binomial_2_log likelihood needs a finite phi > 0')
+    elif phi is not None:
+        raise ValueError('phi is taken by the neg_binomial_2_log likelihood only, not by %r'
+                         % (likelihood,))
+    if not np.all((y >= 0) & (y == np.floor(y))):
+        raise ValueError('the %s likelihood needs non-negative integer y' % likelihood)
+    if np.any(y > 2.0 ** 53):
+        raise ValueError('the %s likelihood needs y <= 2^53' % likelihood)
+    if offset is None:
+        return np.zeros(m)
+    offset = np.asarray(offset, dtype=np.float64)
+    if offset.shape != (m,):
+        raise ValueError('offset must have shape (%d,), got %s' % (m, offset.shape))
+    if not np.all(np.isfinite(offset)):
+        raise ValueError('offset must be finite')
+    return offset
+
+
+def regression(x, y, likelihood='student_t', df=None, scale=1.0, prior_scale=10.0, offset=None,
+               phi=None):
     """A generalised linear model evaluated on the device: beta_d ~ N(0,
     prior_scale^2) independently and, with eta_m = x_m . beta,
       gaussian         y_m ~ N(eta_m, scale^2)
       student_t        y_m ~ t_df(eta_m, scale)
       bernoulli_logit  y_m ~ Bernoulli(logistic(eta_m)), y_m in {0, 1}
+    or, for counts y_m with eta_m = x_m . beta + offset_m (offset = log exposure,
+    default 0),
+      poisson_log         y_m ~ Poisson(exp(eta_m))
+      neg_binomial_2_log  y_m ~ NB(mean mu = exp(eta_m), variance mu + mu^2 / phi), phi
+                          fixed
     with every normalising constant kept.  x is (M, D), y is (M,).  The data are
     packed once into one parameter array (layout in include/viabel_amd.h) that
     the library uploads per run, so no host call happens inside a fit."""
@@ -164,20 +272,27 @@ def regression(x, y, likelihood='student_t', df=None, scale=1.0, prior_scale=10.
     if likelihood == 'student_t':
         if df is None or not (np.isfinite(df) and df > 0):
             raise ValueError('the student_t likelihood needs df > 0')
-    if likelihood != 'bernoulli_logit':
+    count = likelihood in _COUNT_LIKELIHOODS
+    located = likelihood in ('gaussian', 'student_t')
+    if located:
         if not (np.isfinite(scale) and scale > 0):
             raise ValueError('scale must be positive')
-    elif not np.all((y == 0) | (y == 1)):
+    elif likelihood == 'bernoulli_logit' and not np.all((y == 0) | (y == 1)):
         raise ValueError('the bernoulli_logit likelihood needs y in {0, 1}')
     m, d = x.shape
-    params = np.zeros(REGRESSION_HEADER + m * d + m)
+    offset = _check_counts(likelihood, y, offset, phi, m)
+    h = REGRESSION_HEADER
+    params = np.zeros(h + m * d + m + (m + 1 if count else 0))
     params[0] = _LIKELIHOODS[likelihood]
     params[1] = m
-    params[2] = df if likelihood == 'student_t' else 0.0
-    params[3] = scale if likelihood != 'bernoulli_logit' else 0.0
+    params[2] = df if likelihood == 'student_t' else phi if likelihood == 'neg_binomial_2_log' else 0.0
+    params[3] = scale if located else 0.0
     params[4] = prior_scale
-    params[REGRESSION_HEADER:REGRESSION_HEADER + m * d] = x.ravel()
-    params[REGRESSION_HEADER + m * d:] = y
+    params[h:h + m * d] = x.ravel()
+    params[h + m * d:h + m * d + m] = y
+    if count:
+        params[h + m * d + m:h + m * d + 2 * m] = offset
+        params[-1] = count_constant(y, phi)
     t = Target(nat.TARGET_REGRESSION, d, 'regression', params)
     t.likelihood = likelihood
     t.n_obs = m
@@ -193,6 +308,16 @@ def robust_regression(x, y, df, scale=1.0, prior_scale=10.0):
 def logistic_regression(x, y, prior_scale=10.0):
     """y ~ bernoulli_logit(x beta), beta ~ normal(0, prior_scale)."""
     return regression(x, y, 'bernoulli_logit', prior_scale=prior_scale)
+
+
+def poisson_regression(x, y, offset=None, prior_scale=10.0):
+    """y ~ poisson_log(x beta + offset), beta ~ normal(0, prior_scale)."""
+    return regression(x, y, 'poisson_log', prior_scale=prior_scale, offset=offset)
+
+
+def negative_binomial_regression(x, y, phi, offset=None, prior_scale=10.0):
+    """y ~ neg_binomial_2_log(x beta + offset, phi), beta ~ normal(0, prior_scale)."""
+    return regression(x, y, 'neg_binomial_2_log', prior_scale=prior_scale, offset=offset, phi=phi)
 
 
 HIERARCHICAL_HEADER = 8   # doubles before y in a hierarchical target's parameter block
@@ -248,13 +373,15 @@ MULTILEVEL_HEADER = 8   # doubles before X in a multilevel target's parameter bl
 
 
 def multilevel_regression(x, y, group, likelihood='gaussian', df=None, scale=1.0,
-                          prior_scale=10.0, tau_scale=5.0, centered=False, n_groups=None):
+                          prior_scale=10.0, tau_scale=5.0, centered=False, n_groups=None,
+                          offset=None, phi=None):
     """A regression whose intercept varies by group, evaluated on the device:
       beta_d ~ N(0, prior_scale^2), tau ~ half-Cauchy(0, tau_scale)
       centred       a_g ~ N(0, tau^2),               x = [beta (p), log tau, a (G)]
       non-centred   a_g = tau a_tilde_g, a_tilde_g ~ N(0, 1),
                                                      x = [beta (p), log tau, a_tilde (G)]
-      eta_m = x_m . beta + a_group[m], y_m | eta_m as in `regression`
+      eta_m = x_m . beta + a_group[m] (+ offset_m for the count likelihoods),
+      y_m | eta_m as in `regression`
     with every normalising constant and the Jacobian of tau = exp(log tau) kept, so
     D = p + 1 + G.  x is (M, p), y is (M,), group is (M,) integer labels in 0 .. G - 1
     with G = n_groups, or max(group) + 1; a group without observations has its prior
@@ -300,26 +427,33 @@ def multilevel_regression(x, y, group, likelihood='gaussian', df=None, scale=1.0
     if likelihood == 'student_t':
         if df is None or not (np.isfinite(df) and df > 0):
             raise ValueError('the student_t likelihood needs df > 0')
-    if likelihood != 'bernoulli_logit':
+    count = likelihood in _COUNT_LIKELIHOODS
+    located = likelihood in ('gaussian', 'student_t')
+    if located:
         if not (np.isfinite(scale) and scale > 0):
             raise ValueError('scale must be positive')
-    elif not np.all((y == 0) | (y == 1)):
+    elif likelihood == 'bernoulli_logit' and not np.all((y == 0) | (y == 1)):
         raise ValueError('the bernoulli_logit likelihood needs y in {0, 1}')
+    offset = _check_counts(likelihood, y, offset, phi, m)
     order = np.argsort(g, kind='stable')
     offsets = np.concatenate([[0], np.cumsum(np.bincount(g, minlength=n_groups))])
     h = MULTILEVEL_HEADER
-    params = np.zeros(h + m * p + m + n_groups + 1)
+    params = np.zeros(h + m * p + m + n_groups + 1 + (m + 1 if count else 0))
     params[0] = _LIKELIHOODS[likelihood]
     params[1] = m
-    params[2] = df if likelihood == 'student_t' else 0.0
-    params[3] = scale if likelihood != 'bernoulli_logit' else 0.0
+    params[2] = df if likelihood == 'student_t' else phi if likelihood == 'neg_binomial_2_log' else 0.0
+    params[3] = scale if located else 0.0
     params[4] = prior_scale
     params[5] = n_groups
     params[6] = tau_scale
     params[7] = 1.0 if centered else 0.0
     params[h:h + m * p] = x[order].ravel()
     params[h + m * p:h + m * p + m] = y[order]
-    params[h + m * p + m:] = offsets
+    e = h + m * p + m + n_groups + 1
+    params[h + m * p + m:e] = offsets
+    if count:
+        params[e:e + m] = offset[order]
+        params[-1] = count_constant(y, phi)
     t = Target(nat.TARGET_MULTILEVEL, p + 1 + n_groups, 'multilevel_regression', params)
     t.likelihood = likelihood
     t.n_obs = m
@@ -343,6 +477,23 @@ def multilevel_robust_regression(x, y, group, df, scale=1.0, prior_scale=10.0, t
     return multilevel_regression(x, y, group, 'student_t', df=df, scale=scale,
                                  prior_scale=prior_scale, tau_scale=tau_scale, centered=centered,
                                  n_groups=n_groups)
+
+
+def multilevel_poisson_regression(x, y, group, offset=None, prior_scale=10.0, tau_scale=5.0,
+                                  centered=False, n_groups=None):
+    """Random-intercept Poisson regression: multilevel_regression with the poisson_log
+    likelihood."""
+    return multilevel_regression(x, y, group, 'poisson_log', prior_scale=prior_scale,
+                                 tau_scale=tau_scale, centered=centered, n_groups=n_groups,
+                                 offset=offset)
+
+
+def multilevel_negative_binomial_regression(x, y, group, phi, offset=None, prior_scale=10.0,
+                                            tau_scale=5.0, centered=False, n_groups=None):
+    """multilevel_regression with the neg_binomial_2_log likelihood."""
+    return multilevel_regression(x, y, group, 'neg_binomial_2_log', prior_scale=prior_scale,
+                                 tau_scale=tau_scale, centered=centered, n_groups=n_groups,
+                                 offset=offset, phi=phi)
 
 
 def callback(logdensity_and_grad, dim=None, name='callback'):
