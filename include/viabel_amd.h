@@ -126,7 +126,10 @@ enum vb_target_kind {
  *             dispersion, > 0); ignored otherwise
  *   params[3] sigma (gaussian / student_t scale, > 0; ignored for the other likelihoods)
  *   params[4] prior_scale s (> 0): beta_d ~ N(0, s^2) independently
- *   params[5..7] reserved, zero
+ *   params[5] learn: 0 the scale sigma / the dispersion phi is the constant above (every
+ *             block written before this field existed); 1 it is learned (below)
+ *   params[6] s_aux (> 0) when learn = 1; zero otherwise
+ *   params[7] reserved, zero
  *   params[8 ..]          X, row-major [M][D]
  *   params[8 + M*D ..]    y [M]   (bernoulli_logit: 0 or 1; counts: integers >= 0)
  *   n_params = 8 + M*D + M
@@ -134,6 +137,18 @@ enum vb_target_kind {
  *   params[8 + M*D + M ..]   eta0 [M]
  *   params[8 + M*D + 2 M]    c_data
  *   n_params = 8 + M*D + M + M + 1
+ * learn = 1 (likelihoods 0, 1 and 4 only; dim >= 2): the coordinates are x = [beta (p),
+ * lambda], p = dim - 1, lambda = log sigma (0, 1) or log phi (4); X is [M][p] (read p for
+ * D in the offsets above); params[3] and, for likelihood 4, params[2] are ignored (packed as
+ * 0).  theta = e^lambda ~ half-Cauchy(0, s_aux), in lambda with the Jacobian kept and
+ * w = 2 (lambda - log s_aux):  log p(lambda) = log(2 / (pi s_aux)) - softplus(w) + lambda.
+ * The prior of beta runs over the p coefficients.  Likelihood 4 with learn = 1: the data
+ * term sum_m [lgamma(y_m + phi) - lgamma(phi) - y_m log phi] = sum_{j=1}^{J-1} T_j
+ * log1p(j / phi) now depends on a coordinate, so c_data holds only sum_m -lgamma(y_m + 1)
+ * and the table is appended:
+ *   params[8 + M*p + 2 M + 1]      J = max_m y_m (an integer in [0, 65536]; 0: no table)
+ *   params[8 + M*p + 2 M + 2 ..]   T [J], T[j] = #{m : y_m > j}, j = 0 .. J - 1
+ *   n_params = 8 + M*p + M + M + 1 + 1 + J
  * vb_run_create copies the block once into the run; one-shot calls stage a host
  * block per call and read a device block in place. */
 

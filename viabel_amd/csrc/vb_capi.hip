@@ -584,32 +584,69 @@ int regression_head(const vb_target* t, vbk::GlmHead* o) {
   if (!(h[1] >= 1.0 && h[1] <= 9.0e15 && h[1] == std::floor(h[1])))
     return fail(VB_EINVAL, "regression target: params[1] (M) must be an integer >= 1, got %g", h[1]);
   const int lik = (int)h[0];
+  if (!(h[5] == 0.0 || h[5] == 1.0))
+    return fail(VB_EINVAL, "regression target: params[5] (learn) must be 0 or 1, got %g", h[5]);
+  const bool learn = h[5] == 1.0;   // the last coordinate is log sigma (0, 1) or log phi (4)
+  if (learn && (lik == 2 || lik == 3))
+    return fail(VB_EINVAL,
+                "regression target: params[5] (learn) = 1 is valid for the likelihoods 0, 1 and 4 "
+                "(gaussian, student_t, neg_binomial_2_log), not for %d", lik);
+  if (learn && t->dim < 2)
+    return fail(VB_EINVAL, "regression target: params[5] (learn) = 1 needs dim >= 2 (p >= 1 "
+                "coefficients and the log), got %lld", (long long)t->dim);
   if (lik == 1 && !(h[2] > 0.0 && std::isfinite(h[2])))
     return fail(VB_EINVAL, "regression target: params[2] (nu) must be positive, got %g", h[2]);
-  if (lik == 4 && !(h[2] > 0.0 && std::isfinite(h[2])))
+  if (lik == 4 && !learn && !(h[2] > 0.0 && std::isfinite(h[2])))
     return fail(VB_EINVAL, "regression target: params[2] (phi) must be positive, got %g", h[2]);
-  if (lik < 2 && !(h[3] > 0.0 && std::isfinite(h[3])))
+  if (lik < 2 && !learn && !(h[3] > 0.0 && std::isfinite(h[3])))
     return fail(VB_EINVAL, "regression target: params[3] (sigma) must be positive, got %g", h[3]);
   if (!(h[4] > 0.0 && std::isfinite(h[4])))
     return fail(VB_EINVAL, "regression target: params[4] (prior_scale) must be positive, got %g", h[4]);
-  for (int i = 5; i < vbk::kGlmHeader; ++i)
+  if (learn && !(h[6] > 0.0 && std::isfinite(h[6])))
+    return fail(VB_EINVAL, "regression target: params[6] (s_aux) must be positive, got %g", h[6]);
+  for (int i = learn ? 7 : 6; i < vbk::kGlmHeader; ++i)
     if (h[i] != 0.0)
       return fail(VB_EINVAL, "regression target: params[%d] (reserved) must be zero, got %g", i, h[i]);
   const bool count = lik >= 3;   // eta0 [M] and c_data follow y
-  const double want =
-      (double)vbk::kGlmHeader + h[1] * (double)t->dim + h[1] + (count ? h[1] + 1.0 : 0.0);
-  if ((double)t->n_params != want)
+  const double cols = (double)t->dim - (learn ? 1.0 : 0.0);   // of X
+  const double base =
+      (double)vbk::kGlmHeader + h[1] * cols + h[1] + (count ? h[1] + 1.0 : 0.0);
+  // a learned dispersion: J and T [J] follow c_data
+  double J = 0.0;
+  if (learn && lik == 4) {
+    if ((double)t->n_params < base + 1.0)
+      return fail(VB_EINVAL, "regression target: n_params %lld is shorter than 8 + M*p + M + M + 1 + 1 = "
+                  "%.0f (M %.0f, p %.0f)", (long long)t->n_params, base + 1.0, h[1], cols);
+    const double* jp = t->params + (size_t)base;
+    if (pc == 1)
+      VB_HIP(hipMemcpy(&J, jp, sizeof(double), hipMemcpyDeviceToHost));
+    else
+      J = *jp;
+    if (!(J >= 0.0 && J <= 65536.0 && J == std::floor(J)))
+      return fail(VB_EINVAL, "regression target: J (the table's length, after c_data) must be an "
+                  "integer in [0, 65536], got %g", J);
+  }
+  const double want = base + (learn && lik == 4 ? 1.0 + J : 0.0);
+  if ((double)t->n_params != want) {
+    if (learn)
+      return fail(VB_EINVAL, "regression target: n_params %lld does not match 8 + M*p + M%s = %.0f "
+                  "(M %.0f, p = dim - 1 = %.0f)", (long long)t->n_params,
+                  lik == 4 ? " + M + 1 + 1 + J" : "", want, h[1], cols);
     return fail(VB_EINVAL, "regression target: n_params %lld does not match 8 + M*D + M%s = %.0f (M %.0f, dim %lld)",
                 (long long)t->n_params, count ? " + M + 1" : "", want, h[1], (long long)t->dim);
+  }
   o->lik = lik;
   o->M = (long long)h[1];
   o->nu = h[2];
-  o->sigma = h[3];
+  o->sigma = learn ? 0.0 : h[3];
   o->prior = h[4];
-  o->phi = lik == 4 ? h[2] : 0.0;
+  o->phi = lik == 4 && !learn ? h[2] : 0.0;
   o->c_data = 0.0;
+  o->learn = learn ? 1 : 0;
+  o->s_aux = learn ? h[6] : 0.0;
+  o->J = (long long)J;
   if (count) {
-    const double* cp = t->params + (size_t)t->n_params - 1;
+    const double* cp = t->params + (size_t)base - 1;
     if (pc == 1)
       VB_HIP(hipMemcpy(&o->c_data, cp, sizeof(double), hipMemcpyDeviceToHost));
     else

@@ -1575,7 +1575,7 @@ int host_target_eval(FrWork* W, const HostTarget& t, int D, long long n, const d
 int glm_target_eval(FrWork* W, const GlmHead& h, int D, long long n, const double* tparams,
                     const double* x, double* logp, double* grad, hipStream_t st) {
   if (!tparams) return vb_set_error(-1, "regression target without parameters");
-  FR_HIP(W->glm.reserve(sizeof(double) * glm_scratch_doubles(D, n, h.M, grad != nullptr)));
+  FR_HIP(W->glm.reserve(sizeof(double) * glm_scratch_doubles(D, n, h, grad != nullptr)));
   FR_HIP(launch_glm_rows(D, n, h, tparams, x, logp, grad, W->glm.d(), st));
   return 0;
 }

@@ -25,6 +25,22 @@
 //     MFMA operand maps as vb_gemm.hpp: A[l&15][k=l>>4], B[k=l>>4][l&15],
 //     C row = (l>>4) + 4 r, col = l&15.
 //     D > 128: one block per 128-column slab, each recomputing eta.
+//
+// Learned scale / dispersion (the block's `learn` field): the sample rows are [beta (p),
+// lambda], lambda = log sigma (gaussian, student_t) or log phi (neg_binomial_2_log), X is
+// [M][p].  The same two kernels serve it as the instances LIK = 5, 6, 7 (the learned forms
+// of 0, 1, 4), chosen BY p EXACTLY AS A FIXED BLOCK WITH D = p IS: p <= 16 the lane-per-row
+// kernel (DP from p), p > 16 the matrix kernel with NCT and the column slabs from p.
+// Column p (lambda) never enters the R X product: the sample rows have their own stride
+// (p + 1) and their own bound (p).  The link constants depend on the row: a lane of the
+// lane-per-row kernel forms its own in its prologue (one exp); the matrix kernel keeps
+// 16 rows x 2 doubles in LDS behind the waves' tiles (a lane serves the rows lq + 4 r; in
+// registers they would cost 16 VGPRs beside the 8 of the second accumulator) and reads
+// them as broadcasts (16 lanes per address).  sum_m dl/dlambda is a second per-row scalar
+// beside lp: same wave reduction, same wave-order LDS sum, same writer, a partial array
+// pla [nchunk][n] beside plp.  The gaussian needs none: sum_m (-1 + r^2 / sigma^2) =
+// -M - 2 sum_m l_m.  The negative binomial's table sums A(phi) = sum_j T_j log1p(j / phi)
+// and dA/dlambda = -sum_j T_j j / (phi + j) are formed once per call by glm_disp_kernel.
 #include <algorithm>
 #include <cmath>
 
@@ -55,8 +71,21 @@ struct GlmK {
   double* grad;            // [n][D] or null
   double* plp;             // [nchunk][n]      (nchunk > 1)
   double* pg;              // [nchunk][n][D]   (nchunk > 1, grad)
-  const double* eta0;      // [M]: offset of eta (LIK >= 3; not read otherwise)
+  const double* eta0;      // [M]: offset of eta (LIK 3, 4, 7; not read otherwise)
+  // learned mode (LIK >= 5): D above is p, the columns of X; x and grad have Dx = p + 1
+  // columns, column p is lambda
+  int Dx;
+  long long J;             // length of T (LIK 7)
+  double nu, inv_nu;       // student_t (k1, k2 as in glm_link)
+  double ls_aux, Mf;       // log s_aux; M as a double
+  const double* T;         // [J]: T[j] = #{m : y_m > j}
+  double* tab;             // [2][n]: A(phi), dA/dlambda of the rows (LIK 7)
+  double* pla;             // [nchunk][n]  (nchunk > 1, grad; LIK 6, 7)
 };
+
+// the learned instances: LIK = 5, 6, 7 are likelihoods 0, 1, 4 with lambda a coordinate
+constexpr bool glm_learned(int lik) { return lik >= 5; }
+constexpr bool glm_offset(int lik) { return lik == 3 || lik == 4 || lik == 7; }
 
 // l(y, eta) without its constant, and dl / d eta
 template <int LIK>
@@ -94,22 +123,100 @@ __device__ __forceinline__ double glm_final_logp(const GlmK& k, double sum_l, do
   return k.c_all + (sum_l - 0.5 * k.inv_s2 * ss);
 }
 
+// learned mode: a row's link constants from its lambda.  gaussian, student_t: ca =
+// 1 / sigma = exp(-lambda) (the residual is scaled before it is squared, so a residual of
+// exactly 0 stays 0 where sigma^2 leaves the range); neg_binomial: ca = phi, cb = lambda
+template <int LIK>
+__device__ __forceinline__ void glm_row_consts(double lam, double& ca, double& cb) {
+  if constexpr (LIK == 7) {
+    ca = exp(lam);
+    cb = lam;
+  } else {
+    ca = exp(-lam);
+    cb = 0.0;
+  }
+}
+
+// l(y, eta) without its constant and without -lambda, dl / d eta, and the observation's
+// share of dl / d lambda without its -1 (LIK 5: not formed, -M - 2 sum l serves)
+template <int LIK>
+__device__ __forceinline__ void glm_link_aux(const GlmK& k, double ca, double cb, double eta,
+                                             double y, double& l, double& dl, double& dlam) {
+  if constexpr (LIK == 5) {          // q = r / sigma
+    const double q = (y - eta) * ca;
+    l = -0.5 * (q * q);
+    dl = q * ca;
+    dlam = 0.0;
+  } else if constexpr (LIK == 6) {   // t = (nu + 1) q / (nu + q^2): dl = t / sigma, dlam = t q
+    const double q = (y - eta) * ca;
+    const double q2 = q * q;
+    l = -k.k1 * log1p(q2 * k.inv_nu);
+    const double t = k.k2 * q / (k.nu + q2);
+    dl = t * ca;
+    dlam = t * q;
+  } else {                           // phi = ca, zeta = eta - lambda
+    const double z = eta - cb;
+    const double e = exp(-fabs(z));
+    const double yp = y + ca;
+    const double sp = fmax(z, 0.0) + log1p(e);
+    l = y * eta - yp * sp;
+    const double inv = 1.0 / (1.0 + e);
+    const double lg = yp * (z >= 0.0 ? inv : e * inv);
+    dl = y - lg;
+    dlam = lg - ca * sp;             // (y - dl) - phi softplus(zeta)
+  }
+}
+
+// learned mode: log p and d log p / d lambda of one row from its reduced sums: the prior
+// of beta, -M lambda (gaussian, student_t), the half-Cauchy prior of e^lambda with its
+// Jacobian, softplus and the logistic of w = 2 (lambda - log s_aux) from one exp, and the
+// table sums of the negative binomial
+template <int LIK>
+__device__ __forceinline__ void glm_aux_final(const GlmK& k, long long row, double lam,
+                                              double sum_l, double sum_la, double ss, double& lp,
+                                              double& gl) {
+  const double w = 2.0 * (lam - k.ls_aux);
+  const double e = exp(-fabs(w));
+  const double sp = fmax(w, 0.0) + log1p(e);
+  const double inv = 1.0 / (1.0 + e);
+  const double lg = w >= 0.0 ? inv : e * inv;
+  const double v = k.c_all + (sum_l - 0.5 * k.inv_s2 * ss);
+  const double gp = 1.0 - 2.0 * lg;
+  if constexpr (LIK == 7) {
+    lp = v + ((lam - sp) + k.tab[row]);
+    gl = (sum_la + k.tab[k.n + row]) + gp;
+  } else {
+    lp = v + (fma(-k.Mf, lam, lam) - sp);
+    if constexpr (LIK == 5)
+      gl = (-2.0 * sum_l - k.Mf) + gp;
+    else
+      gl = (sum_la - k.Mf) + gp;
+  }
+}
+
 // ---- D <= 16: one lane per sample row ------------------------------------------
 template <int LIK, bool GRAD, int DP>
 __global__ __launch_bounds__(256) void glm_rows_small_kernel(GlmK k) {
   __shared__ double Xs[kGlmTile * DP];
-  constexpr bool OFFS = LIK >= 3;               // eta0 rides behind y in the tile
+  constexpr bool OFFS = glm_offset(LIK);        // eta0 rides behind y in the tile
+  constexpr bool LRN = glm_learned(LIK);
   __shared__ double ys[OFFS ? 2 * kGlmTile : kGlmTile];
   const int t = threadIdx.x, nt = blockDim.x, D = k.D;
+  const int Dx = LRN ? k.Dx : D;                // row stride of x and grad
   const long long row = (long long)blockIdx.x * nt + t;
   const bool live = row < k.n;
   double beta[DP], g[DP];
 #pragma unroll
   for (int d = 0; d < DP; ++d) {
-    beta[d] = (live && d < D) ? k.x[row * D + d] : 0.0;
+    beta[d] = (live && d < D) ? k.x[row * Dx + d] : 0.0;
     g[d] = 0.0;
   }
   double lp = 0.0;
+  double lam = 0.0, ca = 0.0, cb = 0.0, la = 0.0;   // learned mode only
+  if constexpr (LRN) {
+    lam = live ? k.x[row * Dx + D] : 0.0;
+    glm_row_consts<LIK>(lam, ca, cb);
+  }
   const long long m0 = (long long)blockIdx.y * k.chunk_obs;
   const long long m1 = m0 + k.chunk_obs < k.M ? m0 + k.chunk_obs : k.M;
   for (long long mt = m0; mt < m1; mt += kGlmTile) {
@@ -131,7 +238,13 @@ __global__ __launch_bounds__(256) void glm_rows_small_kernel(GlmK k) {
       for (int d = 0; d < DP; ++d) eta = fma(beta[d], xr[d], eta);
       if constexpr (OFFS) eta += ys[kGlmTile + mm];
       double l, dl;
-      glm_link<LIK>(k, eta, ys[mm], l, dl);
+      if constexpr (LRN) {
+        double dlam;
+        glm_link_aux<LIK>(k, ca, cb, eta, ys[mm], l, dl, dlam);
+        if constexpr (GRAD && LIK != 5) la += dlam;
+      } else {
+        glm_link<LIK>(k, eta, ys[mm], l, dl);
+      }
       lp += l;
       if constexpr (GRAD) {
 #pragma unroll
@@ -144,16 +257,24 @@ __global__ __launch_bounds__(256) void glm_rows_small_kernel(GlmK k) {
     double ss = 0.0;
 #pragma unroll
     for (int d = 0; d < DP; ++d) ss = fma(beta[d], beta[d], ss);
-    k.logp[row] = glm_final_logp(k, lp, ss);
+    if constexpr (LRN) {
+      double lpv, gl;
+      glm_aux_final<LIK>(k, row, lam, lp, la, ss, lpv, gl);
+      k.logp[row] = lpv;
+      if constexpr (GRAD) k.grad[row * Dx + D] = gl;
+    } else {
+      k.logp[row] = glm_final_logp(k, lp, ss);
+    }
     if constexpr (GRAD) {
 #pragma unroll
       for (int d = 0; d < DP; ++d)
-        if (d < D) k.grad[row * D + d] = g[d] - beta[d] * k.inv_s2;
+        if (d < D) k.grad[row * Dx + d] = g[d] - beta[d] * k.inv_s2;
     }
   } else {
     const long long pr = (long long)blockIdx.y * k.n + row;
     k.plp[pr] = lp;
     if constexpr (GRAD) {
+      if constexpr (LRN && LIK != 5) k.pla[pr] = la;
 #pragma unroll
       for (int d = 0; d < DP; ++d)
         if (d < D) k.pg[pr * D + d] = g[d];
@@ -162,27 +283,32 @@ __global__ __launch_bounds__(256) void glm_rows_small_kernel(GlmK k) {
 }
 
 // ---- D > 16: 16 sample rows x 16 observations per MFMA tile -----------------------
-// dst [16][kGlmSX] <- src[r0 + i][c0 + j] (row stride D), i < 16, j < 32; zero for
+// dst [16][kGlmSX] <- src[r0 + i][c0 + j] (row stride ld), i < 16, j < 32; zero for
 // rows >= rmax and columns >= D.  One wave.
 __device__ __forceinline__ void glm_stage(double* dst, const double* src, long long r0,
-                                          long long rmax, int c0, int D, int lane) {
+                                          long long rmax, int c0, int D, int ld, int lane) {
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     const int idx = i * 64 + lane, rr = idx >> 5, cc = idx & 31;
     double v = 0.0;
-    if (r0 + rr < rmax && c0 + cc < D) v = src[(r0 + rr) * D + c0 + cc];
+    if (r0 + rr < rmax && c0 + cc < D) v = src[(r0 + rr) * ld + c0 + cc];
     dst[rr * kGlmSX + cc] = v;
   }
 }
 
 template <int LIK, bool GRAD, int NCT>
 __global__ __launch_bounds__(256) void glm_rows_mfma_kernel(GlmK k) {
-  __shared__ double smem[4 * kGlmWave];
+  constexpr bool OFFS = glm_offset(LIK);
+  constexpr bool LRN = glm_learned(LIK);
+  constexpr bool LACC = LRN && GRAD && LIK != 5;   // a second per-row accumulator
+  // learned mode: the 16 rows' link constants (ca, cb) behind the waves' tiles
+  __shared__ double smem[4 * kGlmWave + (LRN ? 32 : 0)];
   const int t = threadIdx.x, w = t >> 6, lane = t & 63, lr = lane & 15, lq = lane >> 4;
   double* Xs = smem + w * kGlmWave;
   double* Bs = Xs + 16 * kGlmSX;
   double* Rs = Bs + 16 * kGlmSX;
   const int D = k.D;
+  const int Dx = LRN ? k.Dx : D;                // row stride of x and grad
   const int nK = (D + kGlmKD - 1) / kGlmKD;
   const long long row0 = (long long)blockIdx.x * 16;
   const int col0 = (int)blockIdx.z * (NCT * 16);
@@ -194,6 +320,16 @@ __global__ __launch_bounds__(256) void glm_rows_mfma_kernel(GlmK k) {
 #pragma unroll
   for (int c = 0; c < NCT; ++c) acc[c] = d4{0.0, 0.0, 0.0, 0.0};
   double lpa[4] = {0.0, 0.0, 0.0, 0.0};
+  double laa[4] = {0.0, 0.0, 0.0, 0.0};          // LACC only
+  if constexpr (LRN) {
+    // read after the first barrier of the loop below (every chunk has a tile)
+    if (t < 16) {
+      double ca, cb;
+      glm_row_consts<LIK>(row0 + t < k.n ? k.x[(row0 + t) * Dx + D] : 0.0, ca, cb);
+      smem[4 * kGlmWave + 2 * t] = ca;
+      smem[4 * kGlmWave + 2 * t + 1] = cb;
+    }
+  }
 
   // every wave runs the same number of rounds (the barriers are block-wide); a wave
   // without a tile in the last round only takes part in the barriers
@@ -205,9 +341,9 @@ __global__ __launch_bounds__(256) void glm_rows_mfma_kernel(GlmK k) {
     for (int kt = 0; kt < nK; ++kt) {
       __syncthreads();
       if (valid) {
-        glm_stage(Xs, k.X, mt, m1, kt * kGlmKD, D, lane);
+        glm_stage(Xs, k.X, mt, m1, kt * kGlmKD, D, D, lane);
         // one slice holds every column: the sample tile is staged once
-        if (nK > 1 || it == 0) glm_stage(Bs, k.x, row0, k.n, kt * kGlmKD, D, lane);
+        if (nK > 1 || it == 0) glm_stage(Bs, k.x, row0, k.n, kt * kGlmKD, D, Dx, lane);
       }
       __syncthreads();
       if (valid) {
@@ -226,14 +362,20 @@ __global__ __launch_bounds__(256) void glm_rows_mfma_kernel(GlmK k) {
       const bool ok = mt + lr < m1;
       const double yv = ok ? k.y[mt + lr] : 0.0;
       double ev = 0.0;
-      if constexpr (LIK >= 3) ev = ok ? k.eta0[mt + lr] : 0.0;
+      if constexpr (OFFS) ev = ok ? k.eta0[mt + lr] : 0.0;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         double l, dl;
-        if constexpr (LIK >= 3)
+        if constexpr (LRN) {
+          const double* rk = smem + 4 * kGlmWave + 2 * (lq + 4 * r);
+          double dlam;
+          glm_link_aux<LIK>(k, rk[0], rk[1], OFFS ? eta[r] + ev : eta[r], yv, l, dl, dlam);
+          if constexpr (LACC) laa[r] += ok ? dlam : 0.0;
+        } else if constexpr (OFFS) {
           glm_link<LIK>(k, eta[r] + ev, yv, l, dl);
-        else
+        } else {
           glm_link<LIK>(k, eta[r], yv, l, dl);
+        }
         lpa[r] += ok ? l : 0.0;
         if constexpr (GRAD) Rs[(lq + 4 * r) * kGlmSR + lr] = ok ? dl : 0.0;
       }
@@ -244,7 +386,7 @@ __global__ __launch_bounds__(256) void glm_rows_mfma_kernel(GlmK k) {
       for (int cs = 0; cs < NCT / 2; ++cs) {
         if (nK > 1) {   // (one slice: Xs already holds the tile's columns 0..31)
           __syncthreads();
-          if (valid) glm_stage(Xs, k.X, mt, m1, col0 + cs * 32, D, lane);
+          if (valid) glm_stage(Xs, k.X, mt, m1, col0 + cs * 32, D, D, lane);
         }
         __syncthreads();
         if (valid) {
@@ -268,25 +410,43 @@ __global__ __launch_bounds__(256) void glm_rows_mfma_kernel(GlmK k) {
   for (int r = 0; r < 4; ++r) {
 #pragma unroll
     for (int off = 8; off >= 1; off >>= 1) lpa[r] += __shfl_xor(lpa[r], off, 64);
+    if constexpr (LACC) {
+#pragma unroll
+      for (int off = 8; off >= 1; off >>= 1) laa[r] += __shfl_xor(laa[r], off, 64);
+    }
   }
   __syncthreads();
   if (lr == 0) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) red[w * 16 + lq + 4 * r] = lpa[r];
+    if constexpr (LACC) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) red[64 + w * 16 + lq + 4 * r] = laa[r];
+    }
   }
   __syncthreads();
   if (blockIdx.z == 0 && t < 16 && row0 + t < k.n) {
     const long long row = row0 + t;
     const double s = ((red[t] + red[16 + t]) + red[32 + t]) + red[48 + t];
+    double sl = 0.0;
+    if constexpr (LACC) sl = ((red[64 + t] + red[80 + t]) + red[96 + t]) + red[112 + t];
     if (fin) {
       double ss = 0.0;
       for (int d = 0; d < D; ++d) {
-        const double b = k.x[row * D + d];
+        const double b = k.x[row * Dx + d];
         ss = fma(b, b, ss);
       }
-      k.logp[row] = glm_final_logp(k, s, ss);
+      if constexpr (LRN) {
+        double lpv, gl;
+        glm_aux_final<LIK>(k, row, k.x[row * Dx + D], s, sl, ss, lpv, gl);
+        k.logp[row] = lpv;
+        if constexpr (GRAD) k.grad[row * Dx + D] = gl;
+      } else {
+        k.logp[row] = glm_final_logp(k, s, ss);
+      }
     } else {
       k.plp[(long long)blockIdx.y * k.n + row] = s;
+      if constexpr (LACC) k.pla[(long long)blockIdx.y * k.n + row] = sl;
     }
   }
   if constexpr (GRAD) {
@@ -301,7 +461,7 @@ __global__ __launch_bounds__(256) void glm_rows_mfma_kernel(GlmK k) {
       if (row < k.n && col < D) {
         const double s = ((red[t] + red[256 + t]) + red[512 + t]) + red[768 + t];
         if (fin)
-          k.grad[row * D + col] = s - k.x[row * D + col] * k.inv_s2;
+          k.grad[row * Dx + col] = s - k.x[row * Dx + col] * k.inv_s2;
         else
           k.pg[((long long)blockIdx.y * k.n + row) * D + col] = s;
       }
@@ -331,6 +491,67 @@ __global__ __launch_bounds__(256) void glm_combine_kernel(GlmK k, int with_grad)
   }
 }
 
+// the same for the learned instances: job i < n also writes d log p / d lambda of row i;
+// job n + j is gradient entry j of the [n][p] coefficient columns
+template <int LIK>
+__global__ __launch_bounds__(256) void glm_combine_aux_kernel(GlmK k, int with_grad) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long nd = k.n * k.D;
+  if (i < k.n) {
+    double s = 0.0, sl = 0.0;
+    for (int c = 0; c < k.nchunk; ++c) s += k.plp[(long long)c * k.n + i];
+    if constexpr (LIK != 5) {
+      if (with_grad)
+        for (int c = 0; c < k.nchunk; ++c) sl += k.pla[(long long)c * k.n + i];
+    }
+    double ss = 0.0;
+    for (int d = 0; d < k.D; ++d) {
+      const double b = k.x[i * k.Dx + d];
+      ss = fma(b, b, ss);
+    }
+    double lpv, gl;
+    glm_aux_final<LIK>(k, i, k.x[i * k.Dx + k.D], s, sl, ss, lpv, gl);
+    k.logp[i] = lpv;
+    if (with_grad) k.grad[i * k.Dx + k.D] = gl;
+  } else if (with_grad && i - k.n < nd) {
+    const long long j = i - k.n, row = j / k.D, col = j % k.D;
+    double s = 0.0;
+    for (int c = 0; c < k.nchunk; ++c) s += k.pg[(long long)c * nd + j];
+    k.grad[row * k.Dx + col] = s - k.x[row * k.Dx + col] * k.inv_s2;
+  }
+}
+
+// learned dispersion: A(phi) = sum_{j=1}^{J-1} T_j log1p(j / phi) and dA / dlambda =
+// -sum_j T_j j / (phi + j) of one sample row per block, phi = exp(lambda) as the row
+// kernels form it.  Every term has one sign.  Threads stride over j; the partial sums
+// meet by the wave reduction and then in wave order: the same bits every call.
+__global__ __launch_bounds__(256) void glm_disp_kernel(GlmK k) {
+  __shared__ double red[8];
+  const long long row = blockIdx.x;
+  const int t = threadIdx.x, w = t >> 6, lane = t & 63;
+  const double phi = exp(k.x[row * k.Dx + k.D]);
+  double a = 0.0, da = 0.0;
+  for (long long j = 1 + t; j < k.J; j += 256) {
+    const double tj = k.T[j], fj = (double)j;
+    a = fma(tj, log1p(fj / phi), a);
+    da = fma(tj, fj / (phi + fj), da);
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    a += __shfl_xor(a, off, 64);
+    da += __shfl_xor(da, off, 64);
+  }
+  if (lane == 0) {
+    red[w] = a;
+    red[4 + w] = da;
+  }
+  __syncthreads();
+  if (t == 0) {
+    k.tab[row] = ((red[0] + red[1]) + red[2]) + red[3];
+    k.tab[k.n + row] = -(((red[4] + red[5]) + red[6]) + red[7]);
+  }
+}
+
 int glm_cu_count() {
   static int cached[64] = {};
   int dev = 0;
@@ -355,8 +576,9 @@ struct GlmPlan {
 // Chunking rule: enough observation chunks that row tiles x chunks reach 4 blocks
 // per CU (a 100-row step fills the chip), none when the row tiles alone do (10^6
 // bound draws); a chunk is a whole number of 64-observation tiles; the partials
-// stay under kGlmScratchMax doubles.
-GlmPlan glm_plan(int D, long long n, long long M, bool grad) {
+// stay under kGlmScratchMax doubles.  A learned block plans with D = p and one more
+// partial per row (pla) beside the gradient's.
+GlmPlan glm_plan(int D, long long n, long long M, bool grad, int extra = 0) {
   GlmPlan p{};
   p.small = D <= kBlockDMax;
   p.tb = p.small ? (n <= 4096 ? 64 : 256) : 256;
@@ -365,7 +587,7 @@ GlmPlan glm_plan(int D, long long n, long long M, bool grad) {
   const long long target = 4LL * glm_cu_count();
   const long long max_chunks = std::min<long long>((M + kGlmTile - 1) / kGlmTile, 1024);
   long long nc = std::max<long long>(1, std::min(max_chunks, (target + p.row_blocks - 1) / p.row_blocks));
-  const long long per = std::max<long long>(1, n) * (1 + (grad ? D : 0));
+  const long long per = std::max<long long>(1, n) * (1 + (grad ? D + extra : 0));
   if (nc > 1 && nc * per > kGlmScratchMax) nc = std::max<long long>(1, kGlmScratchMax / per);
   long long co = (M + nc - 1) / nc;
   co = (co + kGlmTile - 1) / kGlmTile * kGlmTile;
@@ -431,16 +653,102 @@ double lgamma_half_step(double x) {
 
 }  // namespace
 
-size_t glm_scratch_doubles(int D, long long n, long long M, bool grad) {
+size_t glm_scratch_doubles(int D, long long n, const GlmHead& h, bool grad) {
   if (n < 1) return 0;
-  const GlmPlan p = glm_plan(D, n, M, grad);
+  if (h.learn) {   // [tab 2 n (likelihood 4)] [plp] [pla (grad)] [pg (grad)]
+    const int pc = D - 1;
+    const GlmPlan p = glm_plan(pc, n, h.M, grad, 1);
+    const size_t tab = h.lik == 4 ? 2 * (size_t)n : 0;
+    return tab + (p.nchunk > 1 ? (size_t)p.nchunk * (size_t)n * (size_t)(1 + (grad ? 1 + pc : 0)) : 0);
+  }
+  const GlmPlan p = glm_plan(D, n, h.M, grad);
   return p.nchunk > 1 ? (size_t)p.nchunk * (size_t)n * (size_t)(1 + (grad ? D : 0)) : 0;
+}
+
+// the learned block: the instances 5, 6, 7 over p = D - 1 columns
+static hipError_t launch_glm_rows_aux(int D, long long n, const GlmHead& h, const double* params,
+                                      const double* x, double* logp, double* grad,
+                                      double* scratch, hipStream_t s) {
+  const int pc = D - 1;
+  if (pc < 1) return hipErrorInvalidValue;
+  const GlmPlan p = glm_plan(pc, n, h.M, grad != nullptr, 1);
+  if (p.row_blocks > 0x7fffffffLL || p.nslab > 65535 || n > 0x7fffffffLL) return hipErrorInvalidValue;
+  if ((p.nchunk > 1 || h.lik == 4) && !scratch) return hipErrorInvalidValue;
+  GlmK k{};
+  k.D = pc;
+  k.Dx = D;
+  k.nchunk = p.nchunk;
+  k.n = n;
+  k.M = h.M;
+  k.Mf = (double)h.M;
+  k.chunk_obs = p.chunk_obs;
+  const double log2pi = 1.8378770664093454835606594728112;
+  double c_obs = 0.0;   // without -log sigma: -M lambda is the row's
+  if (h.lik == 0) {
+    c_obs = -0.5 * log2pi;
+  } else if (h.lik == 1) {
+    k.nu = h.nu;
+    k.inv_nu = 1.0 / h.nu;
+    k.k1 = 0.5 * (h.nu + 1.0);
+    k.k2 = h.nu + 1.0;
+    c_obs = lgamma_half_step(0.5 * h.nu) - 0.5 * log2pi;
+  }
+  k.inv_s2 = 1.0 / (h.prior * h.prior);
+  k.ls_aux = std::log(h.s_aux);
+  // log(2 / (pi s_aux)): the half-Cauchy's constant
+  k.c_all = -(double)pc * (0.5 * log2pi + std::log(h.prior)) + (double)h.M * c_obs +
+            (-0.45158270528945486472619522989488 - k.ls_aux);
+  if (h.lik == 4) k.c_all += h.c_data;
+  k.X = params + kGlmHeader;
+  k.y = k.X + (size_t)h.M * pc;
+  k.eta0 = h.lik == 4 ? k.y + h.M : nullptr;
+  k.J = h.lik == 4 ? h.J : 0;
+  k.T = h.lik == 4 ? k.eta0 + h.M + 2 : nullptr;   // behind c_data and J
+  k.x = x;
+  k.logp = logp;
+  k.grad = grad;
+  double* sc = scratch;
+  if (h.lik == 4) {
+    k.tab = sc;
+    sc += 2 * (size_t)n;
+  }
+  if (p.nchunk > 1) {
+    k.plp = sc;
+    sc += (size_t)p.nchunk * n;
+    if (grad) {
+      k.pla = sc;
+      k.pg = sc + (size_t)p.nchunk * n;
+    }
+  }
+  if (h.lik == 4) {
+    hipLaunchKernelGGL(glm_disp_kernel, dim3((unsigned)n), dim3(256), 0, s, k);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  if (h.lik == 0)
+    glm_launch<5>(p, k, s);
+  else if (h.lik == 1)
+    glm_launch<6>(p, k, s);
+  else
+    glm_launch<7>(p, k, s);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || p.nchunk == 1) return e;
+  const long long jobs = n + (grad ? n * pc : 0);
+  const dim3 g((unsigned)((jobs + 255) / 256)), b(256);
+  if (h.lik == 0)
+    hipLaunchKernelGGL(glm_combine_aux_kernel<5>, g, b, 0, s, k, grad ? 1 : 0);
+  else if (h.lik == 1)
+    hipLaunchKernelGGL(glm_combine_aux_kernel<6>, g, b, 0, s, k, grad ? 1 : 0);
+  else
+    hipLaunchKernelGGL(glm_combine_aux_kernel<7>, g, b, 0, s, k, grad ? 1 : 0);
+  return hipGetLastError();
 }
 
 hipError_t launch_glm_rows(int D, long long n, const GlmHead& h, const double* params,
                            const double* x, double* logp, double* grad, double* scratch,
                            hipStream_t s) {
   if (n < 1) return hipSuccess;
+  if (h.learn) return launch_glm_rows_aux(D, n, h, params, x, logp, grad, scratch, s);
   const GlmPlan p = glm_plan(D, n, h.M, grad != nullptr);
   if (p.row_blocks > 0x7fffffffLL || p.nslab > 65535) return hipErrorInvalidValue;
   if (p.nchunk > 1 && !scratch) return hipErrorInvalidValue;

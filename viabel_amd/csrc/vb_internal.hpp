@@ -224,12 +224,19 @@ struct GlmHead {
   // likelihoods 3 and 4: the dispersion (4), and the block's last value, the sum of the
   // data-only constants; eta0 [M] follows y in the block
   double phi, c_data;
+  // learn = 1: the last coordinate is lambda = log sigma (likelihoods 0, 1) or log phi (4),
+  // e^lambda ~ half-Cauchy(0, s_aux); X is [M][D - 1]; sigma / phi above are not used.
+  // Likelihood 4: J and T [J] follow c_data in the block (J = 0: no table)
+  int learn;
+  double s_aux;
+  long long J;
 };
 // log p [n] and (grad non-null) d log p / dx [n][D] of the rows of x [n][D] for the
 // regression target whose parameter block is at `params` (device).  scratch holds
-// glm_scratch_doubles(D, n, M, grad != null) doubles of chunk partials (none for
-// one chunk).  Two identical calls give identical bits.
-size_t glm_scratch_doubles(int D, long long n, long long M, bool grad);
+// glm_scratch_doubles(D, n, h, grad != null) doubles: the chunk partials (none for one
+// chunk) and, for a learned dispersion, the table sums of the n rows.  Two identical
+// calls give identical bits.
+size_t glm_scratch_doubles(int D, long long n, const GlmHead& h, bool grad);
 hipError_t launch_glm_rows(int D, long long n, const GlmHead& h, const double* params,
                            const double* x, double* logp, double* grad, double* scratch,
                            hipStream_t s);

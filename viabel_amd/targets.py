@@ -25,6 +25,14 @@ Targets:
                          exp(x_m . beta + offset_m), offset = log exposure
   negative_binomial_regression(x, y, phi, offset=None)
                          ... with the neg_binomial_2_log likelihood (variance mu + mu^2 / phi)
+  regression(..., learn_scale=True) / regression(..., learn_phi=True)
+                         the same models with the gaussian / student_t scale sigma, or the
+                         negative binomial's dispersion phi, learned on the device: x = [beta
+                         (p), lambda], lambda = log sigma or log phi, D = p + 1, e^lambda ~
+                         half-Cauchy(0, hyper_scale)
+  linear_regression(x, y)       gaussian regression with learned sigma
+  robust_regression(x, y, df, learn_scale=True)
+  negative_binomial_regression(x, y, learn_phi=True)
   hierarchical_normal(y, sigma, centered=False, ...)
                          hierarchical normal means over J groups held on the device,
                          x = [mu, log tau, theta or theta_tilde (J)], D = J + 2, centred
@@ -54,7 +62,7 @@ import numpy as np
 from . import _native as nat
 
 __all__ = ['Target', 'isogauss', 'mixture', 'funnel', 'eight_schools_ncp', 'corr_gauss',
-           'regression', 'robust_regression', 'logistic_regression',
+           'regression', 'linear_regression', 'robust_regression', 'logistic_regression',
            'poisson_regression', 'negative_binomial_regression',
            'multilevel_poisson_regression', 'multilevel_negative_binomial_regression',
            'hierarchical_normal', 'eight_schools_cp',
@@ -209,7 +217,32 @@ def count_constant(y, phi=None):
     return math.fsum(terms)
 
 
-def _check_counts(likelihood, y, offset, phi, m):
+DISPERSION_TABLE_MAX = 65536   # largest count y that regression(..., learn_phi=True) takes
+
+
+def dispersion_table(y):
+    """(T, c_data) of the negative binomial with a learned dispersion.  The data term
+    sum_m sum_{j < y_m} log1p(j / phi) of count_constant then depends on the coordinate
+    log phi, so the device forms it per sample row from
+      T[j] = #{m : y_m > j},  j = 0 .. J - 1,  J = max y
+    (sum_m sum_{j<y_m} f(j) = sum_j T[j] f(j); f(0) = 0, so the device's sum starts at j = 1;
+    J = 0 gives an empty table), and c_data keeps only sum_m -lgamma(y_m + 1), each distinct
+    y evaluated once and the sum over m by math.fsum, as count_constant does."""
+    import math
+    y = np.asarray(y, dtype=np.float64)
+    vals, counts = np.unique(y, return_counts=True)
+    jmax = int(vals[-1]) if vals.size else 0
+    above = np.zeros(jmax + 1)                 # above[v] = #{m : y_m == v}
+    above[vals.astype(np.int64)] = counts
+    # T[j] = #{y > j} = M - #{y <= j}
+    table = (y.size - np.cumsum(above))[:jmax].astype(np.float64)
+    terms = []
+    for v, c in zip(vals.tolist(), counts.tolist()):
+        terms += [-math.lgamma(v + 1.0)] * c
+    return table, math.fsum(terms)
+
+
+def _check_counts(likelihood, y, offset, phi, m, learn_phi=False):
     """Validation shared by regression and multilevel_regression for the count
     likelihoods' arguments; returns the offset as a float64 (M,) array (or None)."""
     count = likelihood in _COUNT_LIKELIHOODS
@@ -221,7 +254,11 @@ def _check_counts(likelihood, y, offset, phi, m):
             raise ValueError('phi is taken by the neg_binomial_2_log likelihood only, not by %r'
                              % (likelihood,))
         return None
-    if likelihood == 'neg_binomial_2_log':
+    if likelihood == 'neg_binomial_2_log' and learn_phi:
+        if phi is not None:
+            raise ValueError('learn_phi=True learns the dispersion: phi must be None, got %r'
+                             % (phi,))
+    elif likelihood == 'neg_binomial_2_log':
         if phi is None or not (np.isfinite(phi) and phi > 0):
             raise ValueError('the neg_binomial_2_log likelihood needs a finite phi > 0')
     elif phi is not None:
@@ -242,7 +279,7 @@ def _check_counts(likelihood, y, offset, phi, m):
 
 
 def regression(x, y, likelihood='student_t', df=None, scale=1.0, prior_scale=10.0, offset=None,
-               phi=None):
+               phi=None, learn_scale=False, learn_phi=False, hyper_scale=5.0):
     """A generalised linear model evaluated on the device: beta_d ~ N(0,
     prior_scale^2) independently and, with eta_m = x_m . beta,
       gaussian         y_m ~ N(eta_m, scale^2)
@@ -255,10 +292,27 @@ def regression(x, y, likelihood='student_t', df=None, scale=1.0, prior_scale=10.
                           fixed
     with every normalising constant kept.  x is (M, D), y is (M,).  The data are
     packed once into one parameter array (layout in include/viabel_amd.h) that
-    the library uploads per run, so no host call happens inside a fit."""
+    the library uploads per run, so no host call happens inside a fit.
+
+    Learned scale or dispersion.  learn_scale=True (gaussian, student_t; `scale` is then
+    not used) or learn_phi=True (neg_binomial_2_log; `phi` must then be None) makes the
+    parameter a coordinate: with x of shape (M, p) the target has dim = p + 1 and its
+    coordinate vector is [beta (p), lambda], the last coordinate being the log: lambda =
+    log sigma, or lambda = log phi, with e^lambda ~ half-Cauchy(0, hyper_scale) and the
+    Jacobian of the log kept.  Such a target carries n_coef = p and learned = 'scale' or
+    'phi'; learn_phi needs max(y) <= 65536."""
     if likelihood not in _LIKELIHOODS:
         raise ValueError('unknown likelihood %r (expected one of %s)'
                          % (likelihood, ', '.join(sorted(_LIKELIHOODS))))
+    if learn_scale and likelihood not in ('gaussian', 'student_t'):
+        raise ValueError('learn_scale=True is valid for the gaussian and student_t likelihoods '
+                         'only, not for %r' % (likelihood,))
+    if learn_phi and likelihood != 'neg_binomial_2_log':
+        raise ValueError('learn_phi=True is valid for the neg_binomial_2_log likelihood only, '
+                         'not for %r' % (likelihood,))
+    learn = bool(learn_scale or learn_phi)
+    if learn and not (np.isfinite(hyper_scale) and hyper_scale > 0):
+        raise ValueError('hyper_scale must be positive')
     x = np.asarray(x, dtype=np.float64)
     y = np.asarray(y, dtype=np.float64)
     if x.ndim != 2 or x.shape[0] < 1 or x.shape[1] < 1:
@@ -275,34 +329,66 @@ def regression(x, y, likelihood='student_t', df=None, scale=1.0, prior_scale=10.
     count = likelihood in _COUNT_LIKELIHOODS
     located = likelihood in ('gaussian', 'student_t')
     if located:
-        if not (np.isfinite(scale) and scale > 0):
+        if not learn_scale and not (np.isfinite(scale) and scale > 0):
             raise ValueError('scale must be positive')
     elif likelihood == 'bernoulli_logit' and not np.all((y == 0) | (y == 1)):
         raise ValueError('the bernoulli_logit likelihood needs y in {0, 1}')
     m, d = x.shape
-    offset = _check_counts(likelihood, y, offset, phi, m)
+    offset = _check_counts(likelihood, y, offset, phi, m, learn_phi)
+    table = None
+    if learn_phi:
+        if np.any(y > DISPERSION_TABLE_MAX):
+            raise ValueError('learn_phi=True needs max(y) <= %d, got %g: use the fixed-phi target '
+                             '(negative_binomial_regression(x, y, phi)) for larger counts'
+                             % (DISPERSION_TABLE_MAX, float(np.max(y))))
+        table, c_data = dispersion_table(y)
     h = REGRESSION_HEADER
-    params = np.zeros(h + m * d + m + (m + 1 if count else 0))
+    params = np.zeros(h + m * d + m + (m + 1 if count else 0)
+                      + (1 + table.size if table is not None else 0))
     params[0] = _LIKELIHOODS[likelihood]
     params[1] = m
-    params[2] = df if likelihood == 'student_t' else phi if likelihood == 'neg_binomial_2_log' else 0.0
-    params[3] = scale if located else 0.0
+    params[2] = (df if likelihood == 'student_t'
+                 else phi if likelihood == 'neg_binomial_2_log' and not learn_phi else 0.0)
+    params[3] = scale if located and not learn_scale else 0.0
     params[4] = prior_scale
+    if learn:
+        params[5] = 1.0
+        params[6] = hyper_scale
     params[h:h + m * d] = x.ravel()
     params[h + m * d:h + m * d + m] = y
     if count:
-        params[h + m * d + m:h + m * d + 2 * m] = offset
-        params[-1] = count_constant(y, phi)
-    t = Target(nat.TARGET_REGRESSION, d, 'regression', params)
+        e = h + m * d + 2 * m
+        params[h + m * d + m:e] = offset
+        if learn_phi:
+            params[e] = c_data
+            params[e + 1] = table.size
+            params[e + 2:] = table
+        else:
+            params[e] = count_constant(y, phi)
+    t = Target(nat.TARGET_REGRESSION, d + 1 if learn else d, 'regression', params)
     t.likelihood = likelihood
     t.n_obs = m
+    if learn:
+        t.n_coef = d
+        t.learned = 'scale' if learn_scale else 'phi'
     return t
 
 
-def robust_regression(x, y, df, scale=1.0, prior_scale=10.0):
+def linear_regression(x, y, prior_scale=10.0, hyper_scale=5.0):
+    """Bayesian linear regression with unknown noise: y ~ normal(x beta, sigma), beta ~
+    normal(0, prior_scale), sigma ~ half-Cauchy(0, hyper_scale).  The coordinates are
+    [beta (p), log sigma]: the last one is the log."""
+    return regression(x, y, 'gaussian', prior_scale=prior_scale, learn_scale=True,
+                      hyper_scale=hyper_scale)
+
+
+def robust_regression(x, y, df, scale=1.0, prior_scale=10.0, learn_scale=False, hyper_scale=5.0):
     """The reference's robust-regression model: y ~ student_t(df, x beta, scale),
-    beta ~ normal(0, prior_scale)."""
-    return regression(x, y, 'student_t', df=df, scale=scale, prior_scale=prior_scale)
+    beta ~ normal(0, prior_scale).  learn_scale=True: scale ~ half-Cauchy(0, hyper_scale) is
+    learned, the coordinates are [beta (p), log scale] (the last one is the log) and the
+    `scale` argument is not used."""
+    return regression(x, y, 'student_t', df=df, scale=scale, prior_scale=prior_scale,
+                      learn_scale=learn_scale, hyper_scale=hyper_scale)
 
 
 def logistic_regression(x, y, prior_scale=10.0):
@@ -315,9 +401,15 @@ def poisson_regression(x, y, offset=None, prior_scale=10.0):
     return regression(x, y, 'poisson_log', prior_scale=prior_scale, offset=offset)
 
 
-def negative_binomial_regression(x, y, phi, offset=None, prior_scale=10.0):
-    """y ~ neg_binomial_2_log(x beta + offset, phi), beta ~ normal(0, prior_scale)."""
-    return regression(x, y, 'neg_binomial_2_log', prior_scale=prior_scale, offset=offset, phi=phi)
+def negative_binomial_regression(x, y, phi=None, offset=None, prior_scale=10.0, learn_phi=False,
+                                 hyper_scale=5.0):
+    """y ~ neg_binomial_2_log(x beta + offset, phi), beta ~ normal(0, prior_scale).
+    learn_phi=True (phi left None): phi ~ half-Cauchy(0, hyper_scale) is learned and the
+    coordinates are [beta (p), log phi] (the last one is the log)."""
+    if phi is None and not learn_phi:
+        raise TypeError('negative_binomial_regression() needs phi, or learn_phi=True')
+    return regression(x, y, 'neg_binomial_2_log', prior_scale=prior_scale, offset=offset, phi=phi,
+                      learn_phi=learn_phi, hyper_scale=hyper_scale)
 
 
 HIERARCHICAL_HEADER = 8   # doubles before y in a hierarchical target's parameter block
