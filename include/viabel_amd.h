@@ -371,11 +371,15 @@ int vb_peak_probe(vb_ctx* ctx, int32_t kind, int64_t n, int32_t reps, double* ou
 int vb_math_probe(vb_ctx* ctx, int32_t fn, const double* x, int64_t n, double* out,
                   double* out2);
 /* Launch timing (measurement support, no reference counterpart): with enable
- * != 0 every later vb_run_advance brackets its device work with HIP events on
- * the context's stream, one pair per kernel chunk (column-pair path) or per
- * call (other paths).  vb_run_launch_times waits for that work, returns up to
- * max (steps, milliseconds) records in launch order, n_out = their count, and
- * forgets them. */
+ * != 0 every later vb_run_advance times its device work, one record per kernel
+ * chunk (column-pair path) or per call (other paths).  The column-pair path's
+ * kernels stamp the device's constant 100 MHz clock themselves (resolution
+ * 10 ns): a record runs from the entry of the chunk's first step-kernel block
+ * to the last store of its value reduction, and the host makes no call for it
+ * ahead of the launch.  The other paths bracket the call's work with HIP events
+ * on the context's stream.  vb_run_launch_times waits for the stream's work,
+ * returns up to max (steps, milliseconds) records in launch order, n_out =
+ * their count, and forgets them. */
 int vb_run_set_timing(vb_run* run, int enable);
 int vb_run_launch_times(vb_run* run, int64_t max, int64_t* steps_out, float* ms_out,
                         int64_t* n_out);

@@ -1,5 +1,8 @@
 """A/B of library builds on the headline's launch pair (sep_kernel + sep_values_kernel),
-from the HIP-event launch times bench.py collects (run_cfg3 / vb_run_set_timing).
+from the launch times bench.py collects (run_cfg3 / vb_run_set_timing) and from its wall
+clock.  The launch times are the library's own records -- HIP events up to the build that
+moved them to device stamps, stamps (first block's entry to the value reduction's last
+store) since -- so across that change only the wall figures compare like with like.
 
   python scripts/ab_sep_launch.py [--rounds R] [--steps K --warmup W] LIB_A LIB_B
 
@@ -9,8 +12,9 @@ bench.py's own config-3 run (default: the plain run, 2 000 steps after 100, i.e.
 process of a back-to-back pair measures slower with identical libraries.
 One JSON line per process -- the median and the extremes of its 256-step (or, for short
 runs, its longest) launches, in us -- then a summary line per library: the median over
-processes of those medians, and their spread (max - min).  LIB_A == LIB_B gives the
-spread of the method itself.
+processes of those medians, and their spread (max - min), and the same two figures of
+the wall time per step (bench.py's ms_per_step x 1 000).  LIB_A == LIB_B gives the spread
+of the method itself.
 """
 import argparse
 import json
@@ -55,6 +59,7 @@ def main():
     if len(args.libs) != 2:
         ap.error('two libraries (they may be the same file)')
     med = {0: [], 1: []}
+    wall = {0: [], 1: []}
     for r in range(args.rounds):
         for which in ((0, 1) if r % 2 == 0 else (1, 0)):
             env = dict(os.environ, VIABEL_AMD_LIB=os.path.abspath(args.libs[which]),
@@ -68,11 +73,15 @@ def main():
             rec.update(round=r, side='AB'[which])
             print(json.dumps(rec), flush=True)
             med[which].append(rec['launch_us_median'])
+            wall[which].append(rec['us_per_step_wall'])
     for which in (0, 1):
         print(json.dumps({'side': 'AB'[which], 'lib': os.path.basename(args.libs[which]),
                           'median_of_medians_us': round(statistics.median(med[which]), 2),
                           'spread_us': round(max(med[which]) - min(med[which]), 2),
-                          'medians_us': med[which]}), flush=True)
+                          'medians_us': med[which],
+                          'wall_us_per_step_median': round(statistics.median(wall[which]), 3),
+                          'wall_us_per_step_spread': round(max(wall[which]) - min(wall[which]), 3),
+                          'wall_us_per_step': wall[which]}), flush=True)
 
 
 if __name__ == '__main__':

@@ -15,6 +15,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <deque>
 #include <map>
 #include <mutex>
 #include <new>
@@ -1437,6 +1438,44 @@ struct vb_run {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> evs;
   std::vector<long long> ev_steps;
   size_t ev_used = 0;
+  // the column-pair path's launches are timed by device stamps instead (no host call
+  // ahead of the launch): slot k of the `ev_used` recorded lives in block k /
+  // kStampSlots, a block holding kStampSlots * kStampStripe start words, then
+  // kStampSlots * kStampEnds end words.  Every word has one writer and the host reads
+  // only the words its launch wrote, so a block is set once, when it is made (start ~0:
+  // a grid of fewer than kStampStripe blocks leaves words unwritten).
+  static constexpr size_t kStampSlots = 64;
+  static constexpr size_t kStartWords = kStampSlots * vbk::kStampStripe;
+  static constexpr size_t kEndWords = kStampSlots * vbk::kStampEnds;
+  std::deque<DevBuf> stamp_blocks;
+  int add_stamp_block() {
+    stamp_blocks.emplace_back();
+    DevBuf& b = stamp_blocks.back();
+    int rc = b.reserve((kStartWords + kEndWords) * sizeof(unsigned long long));
+    if (rc == VB_OK) {
+      auto* w = static_cast<unsigned long long*>(b.p);
+      hipError_t e = hipMemsetAsync(w, 0xFF, kStartWords * sizeof(unsigned long long), ctx->stream);
+      if (e == hipSuccess)
+        e = hipMemsetAsync(w + kStartWords, 0, kEndWords * sizeof(unsigned long long), ctx->stream);
+      if (e != hipSuccess) rc = fail(VB_EDEVICE, "hipMemsetAsync failed: %s", hipGetErrorString(e));
+    }
+    if (rc != VB_OK) stamp_blocks.pop_back();
+    return rc;
+  }
+  // the start words of the slot for the next timed launch of k steps (nullptr: timing
+  // off), and its end words
+  int next_stamp(long long k, unsigned long long** out, unsigned long long** out_end) {
+    *out = *out_end = nullptr;
+    if (!timing) return VB_OK;
+    if (ev_used == stamp_blocks.size() * kStampSlots) VB_TRY(add_stamp_block());
+    if (ev_used == ev_steps.size()) ev_steps.push_back(0);
+    ev_steps[ev_used] = k;
+    auto* w = static_cast<unsigned long long*>(stamp_blocks[ev_used / kStampSlots].p);
+    *out = w + (ev_used % kStampSlots) * vbk::kStampStripe;
+    *out_end = w + kStartWords + (ev_used % kStampSlots) * vbk::kStampEnds;
+    ++ev_used;
+    return VB_OK;
+  }
   long long vals_n = 0;   // values in this run's progress snapshot (vb_run_values_async)
   ~vb_run() {
     for (auto& e : evs) {
@@ -1702,21 +1741,20 @@ static int advance_column_pair(vb_ctx* c, vb_run* r, int64_t n_steps, const vbk:
     a.hist = r->hist.d();
     a.vpart = r->vpart.d();
     a.grad = nullptr;
-    std::pair<hipEvent_t, hipEvent_t>* ev;
     HostTrace ht;
-    VB_TRY(r->next_event(cs, &ev));
+    // timed runs: the kernels stamp the launch's slot themselves (sep_kernel's blocks
+    // their entry, sep_values_kernel's the time after their store), so no host call
+    // sits between this call's entry and the launch (the event pair that used to
+    // bracket the launches put 1.2-3.5 us ahead of the doorbell)
+    unsigned long long* stamp_end;
+    VB_TRY(r->next_stamp(cs, &a.stamp, &stamp_end));
     ht.mark();
-    // timed runs: the pair bracketed by event records (hipExtLaunchKernel's own
-    // start / stop stamps instead measured ~0.2 us/step slower on the host path,
-    // interleaved, profiles/r05/headline_ab_c.log)
-    if (ev) VB_HIP(hipEventRecord(ev->first, c->stream));
     VB_HIP(vbk::launch_sep(r->fi.kind, r->tgt, host, a, c->stream));
     ht.mark();
     VB_HIP(vbk::launch_sep_values(a.vpart, cs, a.n_waves, sep_c0(r->fi, a.pd != 0),
-                                  r->values.d() + a.step0, c->stream));
-    if (ev) VB_HIP(hipEventRecord(ev->second, c->stream));
+                                  r->values.d() + a.step0, c->stream, stamp_end));
     ht.mark();
-    ht.print("sep advance: next_event | record + launch_sep | launch_values + record");
+    ht.print("sep advance: next_stamp | launch_sep | launch_values");
     off += cs;
   }
   return VB_OK;
@@ -1877,6 +1915,40 @@ int vb_run_advance(vb_run* r, int64_t n_steps, const vb_noise* noise) {
 int vb_run_set_timing(vb_run* r, int enable) {
   if (!r) return fail(VB_EINVAL, "null vb_run");
   r->timing = enable != 0;
+  // the first block of stamp slots is made and armed here, ahead of the advances
+  if (r->timing && r->path == Path::ColumnPair && r->stamp_blocks.empty()) {
+    VB_TRY(check_ctx(r->ctx));
+    VB_TRY(r->add_stamp_block());
+  }
+  return VB_OK;
+}
+
+// The column-pair path's records: (end - start) of each slot's stamps, in ticks of the
+// 100 MHz clock (10 ns).  A launch's time runs from the entry of its first sep_kernel
+// block to the last store of its sep_values_kernel, so it covers the kernel pair and
+// the boundary between them.
+static int stamp_launch_times(vb_run* r, size_t n, int64_t* steps_out, float* ms_out) {
+  vb_ctx* c = r->ctx;
+  const size_t S = vbk::kStampStripe, E = vbk::kStampEnds, NS = vb_run::kStampSlots;
+  std::vector<unsigned long long> h(vb_run::kStartWords + vb_run::kEndWords);
+  for (size_t b = 0; b * NS < n; ++b) {
+    const size_t used = std::min(NS, n - b * NS);
+    const auto* w = static_cast<const unsigned long long*>(r->stamp_blocks[b].p);
+    VB_HIP(hipMemcpyAsync(h.data(), w, used * S * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                          c->stream));
+    VB_HIP(hipMemcpyAsync(h.data() + vb_run::kStartWords, w + vb_run::kStartWords,
+                          used * E * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    VB_TRY(sync(c));
+    for (size_t j = 0; j < used; ++j) {
+      const size_t k = b * NS + j;
+      const size_t ne = (size_t)std::min<long long>(r->ev_steps[k], (long long)E);
+      unsigned long long t0 = ~0ULL, t1 = 0;
+      for (size_t q = 0; q < S; ++q) t0 = std::min(t0, h[j * S + q]);
+      for (size_t q = 0; q < ne; ++q) t1 = std::max(t1, h[vb_run::kStartWords + j * E + q]);
+      steps_out[k] = r->ev_steps[k];
+      ms_out[k] = t1 > t0 ? (float)((double)(t1 - t0) * 1e-5) : 0.f;   // 10 ns ticks -> ms
+    }
+  }
   return VB_OK;
 }
 
@@ -1886,7 +1958,8 @@ int vb_run_launch_times(vb_run* r, int64_t max, int64_t* steps_out, float* ms_ou
     return fail(VB_EINVAL, "null argument");
   VB_TRY(check_ctx(r->ctx));
   const size_t n = std::min<size_t>(r->ev_used, (size_t)std::max<int64_t>(max, 0));
-  for (size_t k = 0; k < n; ++k) {
+  if (r->path == Path::ColumnPair) VB_TRY(stamp_launch_times(r, n, steps_out, ms_out));
+  for (size_t k = 0; r->path != Path::ColumnPair && k < n; ++k) {
     VB_HIP(hipEventSynchronize(r->evs[k].second));
     float ms = 0.f;
     VB_HIP(hipEventElapsedTime(&ms, r->evs[k].first, r->evs[k].second));

@@ -69,7 +69,21 @@ struct SepArgs {
   const double* noise;    // host noise [n_steps][N][D] or null
   uint32_t k0, k1, stream;
   int pairs2, blocks2, blocks1;  // filled by the launcher (2-pair / 1-pair split)
+  // launch timing (vb_run_set_timing): the kStampStripe start words of this launch's
+  // stamp slot, or null (timing off: the kernel takes no stamp)
+  unsigned long long* stamp;
 };
+
+// Launch-time stamps (the constant 100 MHz clock), written with plain stores, one
+// writer per word: the first kStampStripe blocks of sep_kernel (the blocks dispatched
+// first, one per XCD) store their entry time into start word blockIdx.x, every block of
+// sep_values_kernel the time after its store into end word blockIdx.x (a launch has at
+// most kStampEnds steps); the host takes the min / max.  (Every block folding its time
+// into a shared word with an atomic cost the headline launch ~10 us: ~1 300 blocks'
+// atomics queue at a few addresses ahead of the table barrier,
+// profiles/sep_launch/ab_short_atomics.log.)
+constexpr int kStampStripe = 8;
+constexpr int kStampEnds = 256;
 
 // Arguments of the block-per-problem kernel (any target, D <= kBlockDMax).
 struct BlockArgs {
@@ -113,9 +127,11 @@ bool target_separable(int tgt);
 hipError_t launch_block_predraw(const Family& f, int N, int n_steps, int n_problems,
                                 const Noise& nz, double* noise, double* lq, hipStream_t s);
 
-// values[i] = -(c0 + sum_w vpart[s][w]) for i = step0 + s
+// values[i] = -(c0 + sum_w vpart[s][w]) for i = step0 + s; stamp_end: the launch's
+// kStampEnds end words, or null
 hipError_t launch_sep_values(const double* vpart, int n_steps, int n_waves, double c0,
-                             double* values_at_step0, hipStream_t s);
+                             double* values_at_step0, hipStream_t s,
+                             unsigned long long* stamp_end = nullptr);
 // out[p] = mean over rows of hist [rows][P]   (per problem block of rows)
 hipError_t launch_row_mean(const double* hist, long long rows, long long P, long long n_problems,
                            double* out, hipStream_t s);

@@ -479,6 +479,12 @@ void sep_kernel(SepArgs a) {
   const unsigned long long t_entry = 0;
 #endif
   kernarg_warm(a);   // (every line of the arguments in the first scalar batch)
+  // timed launches: the first blocks' entry times into the slot's start words (one
+  // lane, a store ahead of the table loads; nothing reads it back here)
+  if (a.stamp && blockIdx.x < kStampStripe) {
+    const unsigned long long t_in = __builtin_amdgcn_s_memrealtime();
+    if (threadIdx.x == 0) a.stamp[blockIdx.x] = t_in;
+  }
   __shared__ double s_ring[REGRING ? 1 : 4][REGRING ? 1 : 64 * 4 * PPW_BIG];
   // Box-Muller tables (vb_tables.hpp) for the in-kernel Philox draws
   __shared__ double2 s_sct[HOST ? 1 : kSinCosN];
@@ -518,7 +524,8 @@ void sep_kernel(SepArgs a) {
 constexpr int kValThreads = 1024, kValU = 8;
 __global__ __launch_bounds__(kValThreads) void sep_values_kernel(const double* vpart,
                                                                  int n_waves, double c0,
-                                                                 double* values) {
+                                                                 double* values,
+                                                                 unsigned long long* stamp_end) {
   __shared__ double red[kValThreads / 64];
   const double* row = vpart + (long long)blockIdx.x * n_waves;
   double acc[kValU];
@@ -543,6 +550,9 @@ __global__ __launch_bounds__(kValThreads) void sep_values_kernel(const double* v
 #pragma unroll
     for (int j = 0; j < 4; ++j) r[j] = (red[4 * j] + red[4 * j + 1]) + (red[4 * j + 2] + red[4 * j + 3]);
     values[blockIdx.x] = -(c0 + ((r[0] + r[1]) + (r[2] + r[3])));
+    // timed launches: the time after the store is issued (its write is in flight beside
+    // the stamp's; waiting for it first would put a second memory round trip on the tail)
+    if (stamp_end && blockIdx.x < kStampEnds) stamp_end[blockIdx.x] = __builtin_amdgcn_s_memrealtime();
   }
 }
 
@@ -2635,9 +2645,9 @@ extern "C" int vb_debug_sep_ts(unsigned long long* out, int n_waves) {
 #endif
 
 hipError_t launch_sep_values(const double* vpart, int n_steps, int n_waves, double c0,
-                             double* values, hipStream_t s) {
+                             double* values, hipStream_t s, unsigned long long* stamp_end) {
   hipLaunchKernelGGL(sep_values_kernel, dim3(n_steps), dim3(kValThreads), 0, s, vpart, n_waves,
-                     c0, values);
+                     c0, values, stamp_end);
   return hipGetLastError();
 }
 

@@ -600,7 +600,8 @@ class DeviceRun:
         self.done += int(n_steps)
 
     def set_timing(self, enable=True):
-        """Bracket later advances' device work with HIP events (vb_run_set_timing)."""
+        """Time later advances' device work (vb_run_set_timing: device clock stamps on
+        the column-pair path, HIP events on the others)."""
         nat.check(nat.lib().vb_run_set_timing(self.handle, 1 if enable else 0))
 
     def launch_times(self, max_records=4096):
