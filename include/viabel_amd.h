@@ -100,9 +100,12 @@ enum vb_target_kind {
                                  (layout below), evaluated on the device; any family, any D */
   VB_TARGET_HIERARCHICAL = 7, /* hierarchical normal means over J groups in `params` (layout
                                  below), centred or non-centred; any family, D = J + 2 */
-  VB_TARGET_MULTILEVEL = 8    /* regression with group intercepts sharing a learned scale, data
+  VB_TARGET_MULTILEVEL = 8,   /* regression with group intercepts sharing a learned scale, data
                                  and group offsets in `params` (layout below), centred or
                                  non-centred; any family, D = p + 1 + G */
+  VB_TARGET_PLUGIN = 9        /* the user's model as a gfx950 code object (vb_plugin_load, contract
+                                 below), launched on the device in place of the host callback;
+                                 any family, objective and optimiser */
 };
 
 /* VB_TARGET_REGRESSION: log p(beta) = sum_d log N(beta_d; 0, s^2) + sum_m l(y_m, eta_m),
@@ -202,6 +205,33 @@ enum vb_target_kind {
  *   n_params = 8 + M*p + M + (G + 1) + M + 1
  * Staged and copied as the regression block is. */
 
+/* VB_TARGET_PLUGIN -- device model plugins.  A model is a gfx950 code object (a raw
+ * AMDGPU ELF or the offload bundle `hipcc --genco --offload-arch=gfx950` writes) that
+ * exports two symbols:
+ *   a kernel, named vb_model by default:
+ *     extern "C" __global__ void NAME(const double* x, long long n, int D,
+ *                                     const double* data, long long n_data,
+ *                                     double* logp, double* grad)
+ *       x     [n][D] row-major sample rows (device memory)
+ *       data  the caller's block of n_data doubles (vb_target.params; null and 0 when none)
+ *       logp  [n]
+ *       grad  [n][D], or null for log-weight calls
+ *     The kernel must write every logp[r] and, when grad is non-null, every grad[r][d],
+ *     r < n, and must touch nothing else.
+ *   a launch record:
+ *     extern "C" __device__ const int NAME_launch[3] = {block, rows_per_block, dmax};
+ *     The library launches ceil(n / rows_per_block) blocks of `block` threads on the
+ *     context's stream with no dynamic LDS.  block is a multiple of 64 in [64, 1024],
+ *     rows_per_block >= 1; a target with dim > dmax is refused (dmax = 0: any dimension).
+ * include/viabel_amd_model.h builds both from one device function.
+ * vb_target fields: kind = VB_TARGET_PLUGIN, user = the vb_plugin*, params / n_params = the
+ * data block (host or device memory; staged per one-shot call, copied once into a run, a
+ * device block of a one-shot call is read in place), callback = null.
+ * Checked: the image's bytes before HIP parses them, the launch record, the handle, that it
+ * was loaded on the context's device, dim against dmax.  NOT checked: what the kernel does.
+ * It runs with the library's own pointers, so a kernel that writes out of bounds or never
+ * ends is the model author's fault and takes the process (or the device) with it. */
+
 /* User target: log p and d log p / dx of the n rows of x [n][d] (HOST memory,
  * C order) into logp [n] and grad [n][d]; return 0, or non-zero to abort the
  * call with VB_EDEVICE. */
@@ -234,7 +264,7 @@ typedef struct vb_target {
   const double* params; /* target parameters (host or device), NULL if none */
   int64_t n_params;
   vb_target_callback callback; /* VB_TARGET_CALLBACK only */
-  void* user;
+  void* user;     /* VB_TARGET_CALLBACK: passed to the callback; VB_TARGET_PLUGIN: the vb_plugin* */
 } vb_target;
 
 typedef struct vb_objective {
@@ -291,6 +321,7 @@ typedef struct vb_adagrad_config {
 
 typedef struct vb_ctx vb_ctx;
 typedef struct vb_run vb_run;
+typedef struct vb_plugin vb_plugin;
 
 /* ---- context --------------------------------------------------------- */
 int vb_abi_version(void);
@@ -310,6 +341,27 @@ int vb_ctx_create(int device, void* hip_stream, vb_ctx** out);
 int vb_ctx_destroy(vb_ctx* ctx);
 int vb_ctx_synchronize(vb_ctx* ctx);
 void* vb_ctx_stream(vb_ctx* ctx);
+
+/* ---- device model plugins (VB_TARGET_PLUGIN, contract above) ---------- */
+/* Checks the bytes of a code object without a GPU: ELF64 little-endian for AMDGPU
+ * (e_machine 224) gfx950 (e_flags & 0xff == 0x4f), or an offload bundle holding one under
+ * the id hipv4-amdgcn-amd-amdhsa--gfx950; every offset inside the buffer; `kernel`,
+ * `kernel`.kd and `kernel`_launch in the symbol table; a valid launch record.  VB_EINVAL
+ * with a one-line reason in vb_last_error() otherwise. */
+int vb_plugin_check_image(const void* image, int64_t bytes, const char* kernel);
+/* The same check, then hipModuleLoadData on the context's device, hipModuleGetFunction and
+ * the launch record read back through hipModuleGetGlobal.  The image is not kept.  The
+ * handle is reference-counted: it starts with the caller's reference, a vb_run created on
+ * a plugin target holds another until it is destroyed.  Release the caller's reference
+ * before the context is destroyed. */
+int vb_plugin_load(vb_ctx* ctx, const void* image, int64_t bytes, const char* kernel,
+                   vb_plugin** out);
+/* The launch record (every output nullable). */
+int vb_plugin_info(const vb_plugin* plugin, int32_t* block, int32_t* rows_per_block,
+                   int32_t* dmax);
+/* Drops one reference; the last one synchronises the owning context's stream and unloads
+ * the module. */
+int vb_plugin_release(vb_plugin* plugin);
 
 /* ---- variational family (vb.py:54-65, 148-162) ------------------------ */
 /* x_out[n, d] = sample of q(lambda); n = 0..n-1.  Noise as above (one problem). */

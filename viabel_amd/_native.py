@@ -28,6 +28,7 @@ TARGET_CALLBACK = 5
 TARGET_REGRESSION = 6
 TARGET_HIERARCHICAL = 7
 TARGET_MULTILEVEL = 8
+TARGET_PLUGIN = 9           # a device model plugin: Target.user is its vb_plugin*
 OBJ_KLVI, OBJ_CHIVI, OBJ_KLVI_PD = 0, 1, 2
 OPT_ADAGRAD, OPT_RMSPROP_IA, OPT_ADAM_IA, OPT_RMSPROP_IA_NORM = 0, 1, 2, 3
 NOISE_HOST, NOISE_PHILOX = 0, 1
@@ -80,6 +81,12 @@ _SIGNATURES = {
     'vb_ctx_destroy': ([ctypes.c_void_p], ctypes.c_int),
     'vb_ctx_synchronize': ([ctypes.c_void_p], ctypes.c_int),
     'vb_ctx_stream': ([ctypes.c_void_p], ctypes.c_void_p),
+    'vb_plugin_check_image': ([ctypes.c_char_p, ctypes.c_int64, ctypes.c_char_p], ctypes.c_int),
+    'vb_plugin_load': ([ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int64, ctypes.c_char_p,
+                        P(ctypes.c_void_p)], ctypes.c_int),
+    'vb_plugin_info': ([ctypes.c_void_p, P(ctypes.c_int32), P(ctypes.c_int32),
+                        P(ctypes.c_int32)], ctypes.c_int),
+    'vb_plugin_release': ([ctypes.c_void_p], ctypes.c_int),
     'vb_family_sample': ([ctypes.c_void_p, P(Family), c_double_p, ctypes.c_int64, P(Noise),
                           c_double_p], ctypes.c_int),
     'vb_family_logdensity': ([ctypes.c_void_p, P(Family), c_double_p, c_double_p,
@@ -266,6 +273,11 @@ def release_all():
     under rocprofv3."""
     import gc
     gc.collect()
+    for p in list(_PLUGINS):      # modules are unloaded while their contexts' streams exist
+        try:
+            p.release()
+        except Exception:
+            pass
     for d, c in list(_ctx.items()):
         try:
             c.synchronize()
@@ -281,6 +293,51 @@ def release_all():
 
 
 atexit.register(release_all)
+
+
+def check_plugin_image(image, kernel='vb_model'):
+    """vb_plugin_check_image: raises ValueError with the checker's reason unless `image`
+    (bytes) is a gfx950 code object that exports `kernel` and its launch record.  Needs
+    no GPU."""
+    check(lib().vb_plugin_check_image(image, len(image), kernel.encode()))
+
+
+class Plugin:
+    """One vb_plugin: a model's code object loaded on a context's device.  Holds the
+    caller's reference; runs created on its target hold their own."""
+
+    def __init__(self, ctx, image, kernel='vb_model'):
+        h = ctypes.c_void_p()
+        check(lib().vb_plugin_load(ctx.handle, image, len(image), kernel.encode(),
+                                   ctypes.byref(h)))
+        self.handle, self.ctx = h, ctx
+        _PLUGINS.add(self)
+
+    def info(self):
+        """(block, rows_per_block, dmax) of the launch record."""
+        v = [ctypes.c_int32() for _ in range(3)]
+        check(lib().vb_plugin_info(self.handle, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def usable_on(self, ctx):
+        return bool(self.handle) and self.ctx is ctx and bool(ctx.handle)
+
+    def release(self):
+        """Drop this object's reference (idempotent); returns the library's status."""
+        h, self.handle = self.handle, None
+        _PLUGINS.discard(self)
+        return lib().vb_plugin_release(h) if h else VB_OK
+
+    def __del__(self):
+        try:
+            if self.handle and _lib is not None and not _SHUTDOWN[0]:
+                self.release()
+        except Exception:
+            pass
+
+
+import weakref  # noqa: E402
+_PLUGINS = weakref.WeakSet()
 
 
 _ctx = {}

@@ -330,6 +330,21 @@ void unregister_ctx(vb_ctx* c) {
 
 }  // namespace
 
+int vbk::ctx_device_stream(vb_ctx* c, int* device, hipStream_t* stream) {
+  if (!c) return fail(VB_EINVAL, "null vb_ctx");
+  VB_HIP(hipSetDevice(c->device));
+  *device = c->device;
+  *stream = c->stream;
+  return VB_OK;
+}
+
+int vbk::ctx_synchronize_if_alive(vb_ctx* c) {
+  std::lock_guard<std::mutex> lk(g_ctx_mu);
+  if (!c || !g_live || !g_live->count(c)) return VB_OK;
+  VB_HIP(hipStreamSynchronize(c->stream));
+  return VB_OK;
+}
+
 namespace {
 
 // An input argument: device pointer used directly, host pointer staged.
@@ -785,18 +800,19 @@ struct TargetHeads {
   vbk::GlmHead glm{};
   vbk::HierHead hier{};
   vbk::MlmHead mlm{};
+  vbk::PluginTarget plugin{};
 };
 
 // Whether the target's `params` is a block used whole (regression, hierarchical,
-// multilevel).
+// multilevel, and a plugin's data block, which may be absent).
 bool block_target(int kind) {
   return kind == VB_TARGET_REGRESSION || kind == VB_TARGET_HIERARCHICAL ||
-         kind == VB_TARGET_MULTILEVEL;
+         kind == VB_TARGET_MULTILEVEL || kind == VB_TARGET_PLUGIN;
 }
 
 int check_target(const vb_target* t, int D, TargetHeads* heads = nullptr) {
   if (!t) return fail(VB_EINVAL, "null vb_target");
-  if (t->kind < VB_TARGET_ISOGAUSS || t->kind > VB_TARGET_MULTILEVEL)
+  if (t->kind < VB_TARGET_ISOGAUSS || t->kind > VB_TARGET_PLUGIN)
     return fail(VB_EUNSUPPORTED, "target kind %d is not implemented on the device", t->kind);
   if (t->kind == VB_TARGET_CALLBACK && !t->callback)
     return fail(VB_EINVAL, "callback target needs a callback");
@@ -823,6 +839,17 @@ int check_target(const vb_target* t, int D, TargetHeads* heads = nullptr) {
     vbk::MlmHead h{};
     VB_TRY(multilevel_head(t, &h));
     if (heads) heads->mlm = h;
+  }
+  if (t->kind == VB_TARGET_PLUGIN) {
+    if (t->callback) return fail(VB_EINVAL, "plugin target: callback must be null");
+    if (t->n_params < 0 || (t->n_params > 0 && !t->params) || (t->n_params == 0 && t->params))
+      return fail(VB_EINVAL, "plugin target: params / n_params must be a data block, or null and 0");
+    if (ptr_class(t->params) < 0) return foreign_ptr_error(t->params);
+    int dev = 0;
+    VB_HIP(hipGetDevice(&dev));   // the context's: entry points select it first
+    vbk::PluginTarget p{};
+    VB_TRY(vbk::plugin_view(static_cast<const vb_plugin*>(t->user), dev, t->dim, t->n_params, &p));
+    if (heads) heads->plugin = p;
   }
   return VB_OK;
 }
@@ -950,6 +977,7 @@ vbk::Spec make_spec(const FamInfo& fi, const vb_target* tgt, const vb_objective*
   f.glm = heads.glm;
   f.hier = heads.hier;
   f.mlm = heads.mlm;
+  f.plugin = heads.plugin;
   return f;
 }
 
@@ -1301,6 +1329,12 @@ int vb_target_logdensity(vb_ctx* c, const vb_target* tgt, const double* x, int64
     vbk::FrWork* W;
     VB_TRY(fr_work(c, &W));
     VB_TRY(vbk::mlm_target_eval(W, heads.mlm, D, n, tp, dxx.d, dout.d, dg.d, c->stream));
+  } else if (tgt->kind == VB_TARGET_PLUGIN) {
+    if (n == 0) return VB_OK;
+    const double* tp;
+    double tc;
+    VB_TRY(target_params(c, kSlotGlm, tgt, &tp, &tc));
+    VB_TRY(vbk::plugin_target_eval(heads.plugin, D, n, tp, dxx.d, dout.d, dg.d, c->stream));
   } else if (tgt->kind == VB_TARGET_CORR_GAUSS) {
     if (n == 0) return VB_OK;
     const double* tp;
@@ -1431,6 +1465,7 @@ struct vb_run {
   // full-rank family / materialised mean-field: one value_grad + update per step
   vbk::Spec spec{};
   DevBuf tparams, grad;
+  vb_plugin* plugin = nullptr;  // plugin target: the reference this run holds until destroyed
   DevBuf backup;  // full rank: lambda and the adagrad window at the start of an advance
   long long fr_retries = 0;  // full rank: advances run again after a short warm root
   // launch timing (vb_run_set_timing): event pairs, reused; `ev_used` recorded
@@ -1597,6 +1632,11 @@ int vb_run_create(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const v
   if (e == hipSuccess) e = hipMemsetAsync(r->ring.p, 0, sizeof(double) * P * r->W * n_problems, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e != hipSuccess) return bail(fail(VB_EDEVICE, "run init failed: %s", hipGetErrorString(e)));
+  if (tgt->kind == VB_TARGET_PLUGIN) {
+    vb_plugin* p = static_cast<vb_plugin*>(tgt->user);
+    if ((rc = vbk::plugin_retain(p)) != VB_OK) return bail(rc);
+    r->plugin = p;
+  }
   *out = r;
   return VB_OK;
 }
@@ -2102,8 +2142,10 @@ int vb_run_destroy(vb_run* r) {
     if (r->ctx->pd_stream) (void)hipStreamSynchronize(r->ctx->pd_stream);
     if (r->ctx->blk_stream) (void)hipStreamSynchronize(r->ctx->blk_stream);
   }
+  // the run's reference to its plugin; the last one unloads the module
+  const int rc = r->plugin ? vb_plugin_release(r->plugin) : VB_OK;
   delete r;
-  return VB_OK;
+  return rc;
 }
 
 int vb_adagrad_update(vb_ctx* c, int64_t P, double* lam, const double* grad, double* ring,

@@ -1593,6 +1593,7 @@ int eval_target(FrWork* W, const Spec& f, int D, long long n, const double* x, d
                 double* grad, hipStream_t st) {
   const int tgt = f.tgt;
   if (tgt == kTargetCallback) return host_target_eval(W, f.host, D, n, x, logp, grad, st);
+  if (tgt == kTargetPlugin) return plugin_target_eval(f.plugin, D, n, f.tparams, x, logp, grad, st);
   if (tgt == kTargetRegression)
     return glm_target_eval(W, f.glm, D, n, f.tparams, x, logp, grad, st);
   if (tgt == kTargetHierarchical) {

@@ -221,6 +221,8 @@ hipError_t psis_sumlogs(const double* x, long long n, void* scratch, double* out
 }  // namespace vbk
 
 // ---- full-rank Student-t family (vb_fr.hip) ----------------------------------
+struct vb_ctx;
+struct vb_plugin;
 namespace vbk {
 
 int vb_set_error(int code, const char* fmt, ...);  // defined in vb_capi.hip
@@ -229,6 +231,7 @@ constexpr int kFamilyFrT = 2;
 constexpr int kTargetCorrGauss = 4;
 constexpr int kTargetCallback = 5;
 constexpr int kTargetRegression = 6;
+constexpr int kTargetPlugin = 9;
 // Regression target (vb_glm.hip): host copy of the parameter block's header
 // (include/viabel_amd.h); X [M][D] starts kGlmHeader doubles into the block.
 constexpr int kGlmHeader = 8;
@@ -308,6 +311,25 @@ int host_target_eval(FrWork* W, const HostTarget& t, int D, long long n, const d
                      double* logp, double* grad, hipStream_t st);
 
 
+// Device model plugin (vb_plugin.hip): what a launch of the user's kernel needs, taken
+// from a checked vb_plugin handle.  n_data: doubles in the target's data block.
+struct PluginTarget {
+  hipFunction_t function;
+  int block, rows_per_block;
+  long long n_data;
+};
+// Checks the handle (live, loaded on `device`, dim within its dmax) and fills *out.
+int plugin_view(const vb_plugin* p, int device, long long dim, long long n_data, PluginTarget* out);
+int plugin_retain(vb_plugin* p);   // one more reference (a vb_run's); vb_plugin_release drops it
+// log p [n] and (grad non-null) d log p / dx [n][D] by the plugin's kernel on `st`:
+// ceil(n / rows_per_block) blocks of `block` threads, no dynamic LDS, no synchronisation
+int plugin_target_eval(const PluginTarget& p, int D, long long n, const double* data,
+                       const double* x, double* logp, double* grad, hipStream_t st);
+// (vb_capi.hip) the context's device, selected, and its stream; and a stream
+// synchronisation that a context already destroyed turns into a no-op
+int ctx_device_stream(vb_ctx* c, int* device, hipStream_t* stream);
+int ctx_synchronize_if_alive(vb_ctx* c);
+
 struct FrWork;  // per-context workspace + rocBLAS handle
 FrWork* fr_work_create();
 void fr_work_destroy(FrWork* w);
@@ -325,6 +347,7 @@ struct Spec {
   GlmHead glm;            // tgt == kTargetRegression
   HierHead hier;          // tgt == kTargetHierarchical
   MlmHead mlm;            // tgt == kTargetMultilevel
+  PluginTarget plugin;    // tgt == kTargetPlugin (tparams: its data block)
 };
 
 // All return 0 or a VB_E* code (message via vb_set_error).

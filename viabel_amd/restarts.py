@@ -79,7 +79,7 @@ def _rows_supported(fam, target):
     if fam.kind in nat.CORRELATED_FAMILIES or not isinstance(target, Target):
         return False
     if target.kind in (nat.TARGET_CALLBACK, nat.TARGET_REGRESSION, nat.TARGET_HIERARCHICAL,
-                       nat.TARGET_MULTILEVEL):
+                       nat.TARGET_MULTILEVEL, nat.TARGET_PLUGIN):
         return False
     return target.separable or fam.dim <= _ROWS_DMAX
 

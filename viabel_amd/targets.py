@@ -56,6 +56,13 @@ the model on the HOST once per optimisation step on the whole batch of samples
 (VB_TARGET_CALLBACK); sampling, weights, gradient reductions and the optimiser
 stay on the device.  This is the model boundary, not a fallback of the VI
 computation: the model is the user's code and runs where that code runs.
+
+Device model plugins (VB_TARGET_PLUGIN): device_model(code_object, dim, data) runs the
+user's model ON THE DEVICE -- a gfx950 code object with the kernel contract of
+include/viabel_amd.h, written with include/viabel_amd_model.h and compiled with
+viabel_amd.plugin.compile -- in place of the host callback: no copy, synchronisation or
+Python call per step.  example_model(name, ...) wraps the shipped models of
+viabel_amd/models (robust_regression, banana, isogauss_raw).
 """
 import numpy as np
 
@@ -68,7 +75,8 @@ __all__ = ['Target', 'isogauss', 'mixture', 'funnel', 'eight_schools_ncp', 'corr
            'hierarchical_normal', 'eight_schools_cp',
            'multilevel_regression', 'multilevel_logistic_regression',
            'multilevel_robust_regression',
-           'callback', 'from_stan', 'torch_target', 'as_target']
+           'callback', 'from_stan', 'torch_target', 'as_target',
+           'device_model', 'example_model']
 
 
 class Target:
@@ -659,3 +667,117 @@ def as_target(logdensity, dim):
     if not ok:
         raise TypeError(msg)
     return torch_target(logdensity, int(dim))
+
+
+class DeviceModel(Target):
+    """A device model plugin as a target (see device_model)."""
+
+    def __init__(self, image, dim, data, kernel, name):
+        Target.__init__(self, nat.TARGET_PLUGIN, dim, name)
+        self.image, self.kernel = image, kernel
+        # a device tensor is used in place; anything else is packed as a host block
+        self.data_device = nat.device_tensor(data) if data is not None else None
+        if data is not None and self.data_device is None:
+            self.params = nat.as_f64(np.ravel(np.asarray(data, dtype=np.float64)))
+        # context -> loaded handle; shared by the copies bind() makes
+        self._plugins = {}
+
+    def plugin(self):
+        """The handle loaded on the current context's device (loaded on first use)."""
+        ctx = nat.context()
+        p = self._plugins.get(id(ctx))
+        if p is None or not p.usable_on(ctx):
+            for k in [k for k, v in self._plugins.items() if not v.handle]:
+                del self._plugins[k]      # released with their contexts (release_all)
+            p = self._plugins[id(ctx)] = nat.Plugin(ctx, self.image, self.kernel)
+        return p
+
+    @property
+    def launch(self):
+        """(block, rows_per_block, dmax) as the loaded module reports it."""
+        return self.plugin().info()
+
+    def _struct(self):
+        import ctypes
+        user = ctypes.c_void_p(self.plugin().handle.value)
+        cb = nat.TARGET_CALLBACK_T()
+        if self.data_device is not None:
+            d = self.data_device
+            return nat.Target(self.kind, 0, self.dim, nat.dptr(d), d.numel(), cb, user)
+        if self.params is None:
+            return nat.Target(self.kind, 0, self.dim, None, 0, cb, user)
+        return nat.Target(self.kind, 0, self.dim, nat.dptr(self.params), self.params.size, cb, user)
+
+
+def device_model(code_object, dim=None, data=None, kernel='vb_model', name=None):
+    """A user model evaluated on the device: `code_object` is a gfx950 code object (a
+    path, or its bytes) exporting the kernel `kernel` and the launch record
+    `kernel`_launch (include/viabel_amd.h, "Device model plugins"; write it with
+    include/viabel_amd_model.h and build it with viabel_amd.plugin.compile).
+
+    data   the model's block of doubles, passed to the kernel as (data, n_data): an array
+           (uploaded per run) or a float64 device tensor (used in place), or None
+    dim    the model's dimension; None: the dimension of the family it is used with
+
+    The image is checked here (vb_plugin_check_image), so a file that is not a gfx950 code
+    object with these symbols raises ValueError before any GPU call.  The module is loaded
+    on first use, once per context, and released with it.  The library checks the image,
+    the launch record and the dimension; it cannot check the kernel, which must write
+    logp [n] and grad [n][D] and nothing else."""
+    import os
+    if isinstance(code_object, (bytes, bytearray, memoryview)):
+        image = bytes(code_object)
+    elif isinstance(code_object, (str, os.PathLike)):
+        with open(os.fspath(code_object), 'rb') as f:
+            image = f.read()
+        if name is None:
+            name = os.path.splitext(os.path.basename(os.fspath(code_object)))[0]
+    else:
+        raise TypeError('code_object must be a path or bytes, got %r' % (type(code_object),))
+    if not isinstance(kernel, str):
+        raise TypeError('kernel must be a string')
+    if dim is not None and int(dim) < 1:
+        raise ValueError('dim must be positive')
+    nat.check_plugin_image(image, kernel)
+    return DeviceModel(image, dim, data, kernel, name or 'device_model')
+
+
+def robust_regression_block(x, y, df):
+    """The data block of models/robust_regression.hip: [M, nu, X [M][D], y [M]]."""
+    x = np.asarray(x, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    if x.ndim != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError('x must be a non-empty (M, D) matrix, got shape %s' % (x.shape,))
+    if y.shape != (x.shape[0],):
+        raise ValueError('y must have shape (%d,), got %s' % (x.shape[0], y.shape))
+    if not (np.isfinite(df) and df > 0):
+        raise ValueError('df must be positive')
+    return np.concatenate([[float(x.shape[0]), float(df)], x.ravel(), y])
+
+
+def example_model(name, *args, **kwargs):
+    """The shipped example models (viabel_amd/models/*.hip) as device_model targets:
+      example_model('robust_regression', x, y, df)   beta ~ normal(0, 10), y ~ student_t(df,
+                                                     x beta, 1), Stan's constants dropped;
+                                                     D = x.shape[1] <= 32
+      example_model('banana', dim, scale=10.0, curvature=0.03)    a twisted Gaussian, dim >= 1
+      example_model('isogauss_raw', dim)             N(0, I), the hand-written raw kernel"""
+    from . import plugin
+    if name == 'robust_regression':
+        def pack(x, y, df):
+            return int(np.shape(x)[1]), robust_regression_block(x, y, df)
+        dim, data = pack(*args, **kwargs)
+    elif name == 'banana':
+        def pack(dim, scale=10.0, curvature=0.03):
+            if not (np.isfinite(scale) and scale > 0):
+                raise ValueError('scale must be positive')
+            return int(dim), np.array([scale, curvature], dtype=np.float64)
+        dim, data = pack(*args, **kwargs)
+    elif name == 'isogauss_raw':
+        def pack(dim):
+            return int(dim), None
+        dim, data = pack(*args, **kwargs)
+    else:
+        raise ValueError("unknown example model %r (expected 'robust_regression', 'banana' or "
+                         "'isogauss_raw')" % (name,))
+    return device_model(plugin.shipped(name), dim, data, name=name)

@@ -984,6 +984,8 @@ def _ia_finish(lams, hists, values, log_norms, n_iters, K, rhat_window, r_mean_t
     chains = np.stack(hists, axis=0)
     rhats = functions.compute_R_hat_adaptive_numpy(chains, window_size=rhat_window)
     rhats_halfway = functions.compute_R_hat_halfway(chains, interval=100, start=200)
+    if rhats_halfway.ndim == 1:     # a history shorter than 300 rows has no halfway segment
+        rhats_halfway = rhats_halfway.reshape(0, chains.shape[2])
     rm, rs = rhats[:, :K], rhats[:, K:]
     start_m, start_s = _ia_avg_starts(rm, rs, n_iters, rhat_window, r_mean_threshold,
                                       r_sigma_threshold, tail_avg_iters)
