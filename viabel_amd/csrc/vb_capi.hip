@@ -582,26 +582,78 @@ int check_family(const vb_family* f, FamInfo* o) {
   return VB_OK;
 }
 
+// The 8-value header of a target's parameter block (include/viabel_amd.h) on the host,
+// and the reads and field checks that the block readers below share.  A refusal names
+// the target, the slot and its field: "<name> target: params[i] (field) must ..., got v".
+constexpr int kBlockHeader = 8;
+static_assert(vbk::kGlmHeader == kBlockHeader && vbk::kHierHeader == kBlockHeader &&
+              vbk::kMlmHeader == kBlockHeader, "the block readers share one header length");
+struct BlockHead {
+  const vb_target* t;
+  const char* name;
+  int pc;   // ptr_class of t->params
+  double h[kBlockHeader];
+
+  // n values at params + at, from host or device memory
+  int read(size_t at, double* dst, size_t n = 1) const {
+    if (pc == 1)
+      VB_HIP(hipMemcpy(dst, t->params + at, n * sizeof(double), hipMemcpyDeviceToHost));
+    else
+      std::memcpy(dst, t->params + at, n * sizeof(double));
+    return VB_OK;
+  }
+  int open(const vb_target* target, const char* target_name) {
+    t = target;
+    name = target_name;
+    if (!t->params || t->n_params < kBlockHeader)
+      return fail(VB_EINVAL, "%s target: n_params %lld is shorter than the %d-value header", name,
+                  (long long)t->n_params, kBlockHeader);
+    pc = ptr_class(t->params);
+    if (pc < 0) return foreign_ptr_error(t->params);
+    return read(0, h, kBlockHeader);
+  }
+  int positive(int i, const char* field) const {
+    if (h[i] > 0.0 && std::isfinite(h[i])) return VB_OK;
+    return fail(VB_EINVAL, "%s target: params[%d] (%s) must be positive, got %g", name, i, field, h[i]);
+  }
+  // an integer in [1, max]
+  int count(int i, const char* field, double max) const {
+    if (h[i] >= 1.0 && h[i] <= max && h[i] == std::floor(h[i])) return VB_OK;
+    return fail(VB_EINVAL, "%s target: params[%d] (%s) must be an integer >= 1, got %g", name, i, field,
+                h[i]);
+  }
+  // one of 0, 1, .., max
+  int choice(int i, const char* field, int max) const {
+    if (h[i] >= 0.0 && h[i] <= (double)max && h[i] == std::floor(h[i])) return VB_OK;
+    std::string set = "0";
+    for (int v = 1; v <= max; ++v) set += (v == max ? " or " : ", ") + std::to_string(v);
+    return fail(VB_EINVAL, "%s target: params[%d] (%s) must be %s, got %g", name, i, field, set.c_str(),
+                h[i]);
+  }
+  int reserved(int from) const {
+    for (int i = from; i < kBlockHeader; ++i)
+      if (h[i] != 0.0)
+        return fail(VB_EINVAL, "%s target: params[%d] (reserved) must be zero, got %g", name, i, h[i]);
+    return VB_OK;
+  }
+  // the count likelihoods' data-only constant, the last value of a fixed block
+  int c_data(size_t at, double* v) const {
+    VB_TRY(read(at, v));
+    if (std::isfinite(*v)) return VB_OK;
+    return fail(VB_EINVAL, "%s target: the last value (c_data) must be finite, got %g", name, *v);
+  }
+};
+
 // Header of a regression target's parameter block (include/viabel_amd.h), read from
 // host or device memory and checked against n_params and dim.
 int regression_head(const vb_target* t, vbk::GlmHead* o) {
-  if (!t->params || t->n_params < vbk::kGlmHeader)
-    return fail(VB_EINVAL, "regression target: n_params %lld is shorter than the %d-value header",
-                (long long)t->n_params, vbk::kGlmHeader);
-  double h[vbk::kGlmHeader];
-  const int pc = ptr_class(t->params);
-  if (pc < 0) return foreign_ptr_error(t->params);
-  if (pc == 1)
-    VB_HIP(hipMemcpy(h, t->params, sizeof h, hipMemcpyDeviceToHost));
-  else
-    std::memcpy(h, t->params, sizeof h);
-  if (!(h[0] == 0.0 || h[0] == 1.0 || h[0] == 2.0 || h[0] == 3.0 || h[0] == 4.0))
-    return fail(VB_EINVAL, "regression target: params[0] (likelihood) must be 0, 1, 2, 3 or 4, got %g", h[0]);
-  if (!(h[1] >= 1.0 && h[1] <= 9.0e15 && h[1] == std::floor(h[1])))
-    return fail(VB_EINVAL, "regression target: params[1] (M) must be an integer >= 1, got %g", h[1]);
+  BlockHead b;
+  VB_TRY(b.open(t, "regression"));
+  const double* h = b.h;
+  VB_TRY(b.choice(0, "likelihood", 4));
+  VB_TRY(b.count(1, "M", 9.0e15));
   const int lik = (int)h[0];
-  if (!(h[5] == 0.0 || h[5] == 1.0))
-    return fail(VB_EINVAL, "regression target: params[5] (learn) must be 0 or 1, got %g", h[5]);
+  VB_TRY(b.choice(5, "learn", 1));
   const bool learn = h[5] == 1.0;   // the last coordinate is log sigma (0, 1) or log phi (4)
   if (learn && (lik == 2 || lik == 3))
     return fail(VB_EINVAL,
@@ -610,19 +662,12 @@ int regression_head(const vb_target* t, vbk::GlmHead* o) {
   if (learn && t->dim < 2)
     return fail(VB_EINVAL, "regression target: params[5] (learn) = 1 needs dim >= 2 (p >= 1 "
                 "coefficients and the log), got %lld", (long long)t->dim);
-  if (lik == 1 && !(h[2] > 0.0 && std::isfinite(h[2])))
-    return fail(VB_EINVAL, "regression target: params[2] (nu) must be positive, got %g", h[2]);
-  if (lik == 4 && !learn && !(h[2] > 0.0 && std::isfinite(h[2])))
-    return fail(VB_EINVAL, "regression target: params[2] (phi) must be positive, got %g", h[2]);
-  if (lik < 2 && !learn && !(h[3] > 0.0 && std::isfinite(h[3])))
-    return fail(VB_EINVAL, "regression target: params[3] (sigma) must be positive, got %g", h[3]);
-  if (!(h[4] > 0.0 && std::isfinite(h[4])))
-    return fail(VB_EINVAL, "regression target: params[4] (prior_scale) must be positive, got %g", h[4]);
-  if (learn && !(h[6] > 0.0 && std::isfinite(h[6])))
-    return fail(VB_EINVAL, "regression target: params[6] (s_aux) must be positive, got %g", h[6]);
-  for (int i = learn ? 7 : 6; i < vbk::kGlmHeader; ++i)
-    if (h[i] != 0.0)
-      return fail(VB_EINVAL, "regression target: params[%d] (reserved) must be zero, got %g", i, h[i]);
+  if (lik == 1) VB_TRY(b.positive(2, "nu"));
+  if (lik == 4 && !learn) VB_TRY(b.positive(2, "phi"));
+  if (lik < 2 && !learn) VB_TRY(b.positive(3, "sigma"));
+  VB_TRY(b.positive(4, "prior_scale"));
+  if (learn) VB_TRY(b.positive(6, "s_aux"));
+  VB_TRY(b.reserved(learn ? 7 : 6));
   const bool count = lik >= 3;   // eta0 [M] and c_data follow y
   const double cols = (double)t->dim - (learn ? 1.0 : 0.0);   // of X
   const double base =
@@ -633,11 +678,7 @@ int regression_head(const vb_target* t, vbk::GlmHead* o) {
     if ((double)t->n_params < base + 1.0)
       return fail(VB_EINVAL, "regression target: n_params %lld is shorter than 8 + M*p + M + M + 1 + 1 = "
                   "%.0f (M %.0f, p %.0f)", (long long)t->n_params, base + 1.0, h[1], cols);
-    const double* jp = t->params + (size_t)base;
-    if (pc == 1)
-      VB_HIP(hipMemcpy(&J, jp, sizeof(double), hipMemcpyDeviceToHost));
-    else
-      J = *jp;
+    VB_TRY(b.read((size_t)base, &J));
     if (!(J >= 0.0 && J <= 65536.0 && J == std::floor(J)))
       return fail(VB_EINVAL, "regression target: J (the table's length, after c_data) must be an "
                   "integer in [0, 65536], got %g", J);
@@ -661,42 +702,21 @@ int regression_head(const vb_target* t, vbk::GlmHead* o) {
   o->learn = learn ? 1 : 0;
   o->s_aux = learn ? h[6] : 0.0;
   o->J = (long long)J;
-  if (count) {
-    const double* cp = t->params + (size_t)base - 1;
-    if (pc == 1)
-      VB_HIP(hipMemcpy(&o->c_data, cp, sizeof(double), hipMemcpyDeviceToHost));
-    else
-      o->c_data = *cp;
-    if (!std::isfinite(o->c_data))
-      return fail(VB_EINVAL, "regression target: the last value (c_data) must be finite, got %g", o->c_data);
-  }
+  if (count) VB_TRY(b.c_data((size_t)base - 1, &o->c_data));
   return VB_OK;
 }
 
 // Header of a hierarchical target's parameter block (include/viabel_amd.h), read from
 // host or device memory and checked against n_params and dim.
 int hierarchical_head(const vb_target* t, vbk::HierHead* o) {
-  if (!t->params || t->n_params < vbk::kHierHeader)
-    return fail(VB_EINVAL, "hierarchical target: n_params %lld is shorter than the %d-value header",
-                (long long)t->n_params, vbk::kHierHeader);
-  double h[vbk::kHierHeader];
-  const int pc = ptr_class(t->params);
-  if (pc < 0) return foreign_ptr_error(t->params);
-  if (pc == 1)
-    VB_HIP(hipMemcpy(h, t->params, sizeof h, hipMemcpyDeviceToHost));
-  else
-    std::memcpy(h, t->params, sizeof h);
-  if (!(h[0] == 0.0 || h[0] == 1.0))
-    return fail(VB_EINVAL, "hierarchical target: params[0] (form) must be 0 or 1, got %g", h[0]);
-  if (!(h[1] >= 1.0 && h[1] <= 2.0e9 && h[1] == std::floor(h[1])))
-    return fail(VB_EINVAL, "hierarchical target: params[1] (J) must be an integer >= 1, got %g", h[1]);
-  if (!(h[2] > 0.0 && std::isfinite(h[2])))
-    return fail(VB_EINVAL, "hierarchical target: params[2] (mu_scale) must be positive, got %g", h[2]);
-  if (!(h[3] > 0.0 && std::isfinite(h[3])))
-    return fail(VB_EINVAL, "hierarchical target: params[3] (tau_scale) must be positive, got %g", h[3]);
-  for (int i = 4; i < vbk::kHierHeader; ++i)
-    if (h[i] != 0.0)
-      return fail(VB_EINVAL, "hierarchical target: params[%d] (reserved) must be zero, got %g", i, h[i]);
+  BlockHead b;
+  VB_TRY(b.open(t, "hierarchical"));
+  const double* h = b.h;
+  VB_TRY(b.choice(0, "form", 1));
+  VB_TRY(b.count(1, "J", 2.0e9));
+  VB_TRY(b.positive(2, "mu_scale"));
+  VB_TRY(b.positive(3, "tau_scale"));
+  VB_TRY(b.reserved(4));
   const double want = (double)vbk::kHierHeader + 2.0 * h[1];
   if ((double)t->n_params != want)
     return fail(VB_EINVAL, "hierarchical target: n_params %lld does not match 8 + 2*J = %.0f (J %.0f)",
@@ -715,35 +735,19 @@ int hierarchical_head(const vb_target* t, vbk::HierHead* o) {
 // (include/viabel_amd.h), read from host or device memory and checked against n_params
 // and dim.
 int multilevel_head(const vb_target* t, vbk::MlmHead* o) {
-  if (!t->params || t->n_params < vbk::kMlmHeader)
-    return fail(VB_EINVAL, "multilevel target: n_params %lld is shorter than the %d-value header",
-                (long long)t->n_params, vbk::kMlmHeader);
-  double h[vbk::kMlmHeader];
-  const int pc = ptr_class(t->params);
-  if (pc < 0) return foreign_ptr_error(t->params);
-  if (pc == 1)
-    VB_HIP(hipMemcpy(h, t->params, sizeof h, hipMemcpyDeviceToHost));
-  else
-    std::memcpy(h, t->params, sizeof h);
-  if (!(h[0] == 0.0 || h[0] == 1.0 || h[0] == 2.0 || h[0] == 3.0 || h[0] == 4.0))
-    return fail(VB_EINVAL, "multilevel target: params[0] (likelihood) must be 0, 1, 2, 3 or 4, got %g", h[0]);
-  if (!(h[1] >= 1.0 && h[1] <= 9.0e15 && h[1] == std::floor(h[1])))
-    return fail(VB_EINVAL, "multilevel target: params[1] (M) must be an integer >= 1, got %g", h[1]);
+  BlockHead b;
+  VB_TRY(b.open(t, "multilevel"));
+  const double* h = b.h;
+  VB_TRY(b.choice(0, "likelihood", 4));
+  VB_TRY(b.count(1, "M", 9.0e15));
   const int lik = (int)h[0];
-  if (lik == 1 && !(h[2] > 0.0 && std::isfinite(h[2])))
-    return fail(VB_EINVAL, "multilevel target: params[2] (nu) must be positive, got %g", h[2]);
-  if (lik == 4 && !(h[2] > 0.0 && std::isfinite(h[2])))
-    return fail(VB_EINVAL, "multilevel target: params[2] (phi) must be positive, got %g", h[2]);
-  if (lik < 2 && !(h[3] > 0.0 && std::isfinite(h[3])))
-    return fail(VB_EINVAL, "multilevel target: params[3] (sigma) must be positive, got %g", h[3]);
-  if (!(h[4] > 0.0 && std::isfinite(h[4])))
-    return fail(VB_EINVAL, "multilevel target: params[4] (prior_scale) must be positive, got %g", h[4]);
-  if (!(h[5] >= 1.0 && h[5] <= 2.0e9 && h[5] == std::floor(h[5])))
-    return fail(VB_EINVAL, "multilevel target: params[5] (G) must be an integer >= 1, got %g", h[5]);
-  if (!(h[6] > 0.0 && std::isfinite(h[6])))
-    return fail(VB_EINVAL, "multilevel target: params[6] (tau_scale) must be positive, got %g", h[6]);
-  if (!(h[7] == 0.0 || h[7] == 1.0))
-    return fail(VB_EINVAL, "multilevel target: params[7] (form) must be 0 or 1, got %g", h[7]);
+  if (lik == 1) VB_TRY(b.positive(2, "nu"));
+  if (lik == 4) VB_TRY(b.positive(2, "phi"));
+  if (lik < 2) VB_TRY(b.positive(3, "sigma"));
+  VB_TRY(b.positive(4, "prior_scale"));
+  VB_TRY(b.count(5, "G", 2.0e9));
+  VB_TRY(b.positive(6, "tau_scale"));
+  VB_TRY(b.choice(7, "form", 1));
   const double p = (double)t->dim - 1.0 - h[5];
   if (!(p >= 1.0))
     return fail(VB_EINVAL, "multilevel target: dim %lld does not leave p >= 1 beside 1 + G = %.0f",
@@ -757,12 +761,8 @@ int multilevel_head(const vb_target* t, vbk::MlmHead* o) {
                 "p %.0f, G %.0f)", (long long)t->n_params, count ? " + M + 1" : "", want, h[1], p, h[5]);
   // the group offsets: exact integers, 0 first, M last, non-decreasing
   const size_t ng = (size_t)h[5] + 1;
-  const double* offp = t->params + (size_t)(want - tail - (double)ng);
   std::vector<double> off(ng);
-  if (pc == 1)
-    VB_HIP(hipMemcpy(off.data(), offp, sizeof(double) * ng, hipMemcpyDeviceToHost));
-  else
-    std::memcpy(off.data(), offp, sizeof(double) * ng);
+  VB_TRY(b.read((size_t)(want - tail - (double)ng), off.data(), ng));
   if (off[0] != 0.0)
     return fail(VB_EINVAL, "multilevel target: the first group offset must be 0, got %g", off[0]);
   if (off[ng - 1] != h[1])
@@ -783,15 +783,7 @@ int multilevel_head(const vb_target* t, vbk::MlmHead* o) {
   o->tau_scale = h[6];
   o->phi = lik == 4 ? h[2] : 0.0;
   o->c_data = 0.0;
-  if (count) {
-    const double* cp = t->params + (size_t)t->n_params - 1;
-    if (pc == 1)
-      VB_HIP(hipMemcpy(&o->c_data, cp, sizeof(double), hipMemcpyDeviceToHost));
-    else
-      o->c_data = *cp;
-    if (!std::isfinite(o->c_data))
-      return fail(VB_EINVAL, "multilevel target: the last value (c_data) must be finite, got %g", o->c_data);
-  }
+  if (count) VB_TRY(b.c_data((size_t)t->n_params - 1, &o->c_data));
   return VB_OK;
 }
 

@@ -46,6 +46,7 @@
 
 #include "../../include/viabel_amd.h"
 #include "vb_internal.hpp"
+#include "vb_links.hpp"
 
 namespace vbk {
 namespace {
@@ -62,7 +63,7 @@ constexpr long long kGlmScratchMax = 32LL << 20;          // doubles of chunk pa
 struct GlmK {
   int D, nchunk;
   long long n, M, chunk_obs;
-  double k0, k1, k2, k3;   // link constants (glm_link)
+  LinkK lk;                // link constants (vb_links.hpp)
   double inv_s2, c_all;    // prior precision; every constant of log p (prior + M observations)
   const double* X;         // [M][D]
   const double* y;         // [M]
@@ -76,7 +77,7 @@ struct GlmK {
   // columns, column p is lambda
   int Dx;
   long long J;             // length of T (LIK 7)
-  double nu, inv_nu;       // student_t (k1, k2 as in glm_link)
+  double nu, inv_nu;       // student_t (lk.k1, lk.k2 as in obs_link)
   double ls_aux, Mf;       // log s_aux; M as a double
   const double* T;         // [J]: T[j] = #{m : y_m > j}
   double* tab;             // [2][n]: A(phi), dA/dlambda of the rows (LIK 7)
@@ -85,39 +86,7 @@ struct GlmK {
 
 // the learned instances: LIK = 5, 6, 7 are likelihoods 0, 1, 4 with lambda a coordinate
 constexpr bool glm_learned(int lik) { return lik >= 5; }
-constexpr bool glm_offset(int lik) { return lik == 3 || lik == 4 || lik == 7; }
-
-// l(y, eta) without its constant, and dl / d eta
-template <int LIK>
-__device__ __forceinline__ void glm_link(const GlmK& k, double eta, double y, double& l,
-                                         double& dl) {
-  if constexpr (LIK == 0) {          // gaussian: k0 = 1 / sigma^2
-    const double r = y - eta;
-    l = -0.5 * k.k0 * (r * r);
-    dl = k.k0 * r;
-  } else if constexpr (LIK == 1) {   // student_t: k0 = 1 / (nu sigma^2), k1 = (nu + 1) / 2,
-    const double r = y - eta;        //            k2 = nu + 1, k3 = nu sigma^2
-    const double r2 = r * r;
-    l = -k.k1 * log1p(r2 * k.k0);
-    dl = k.k2 * r / (k.k3 + r2);
-  } else if constexpr (LIK == 2) {   // bernoulli_logit: softplus and the logistic from one exp
-    const double e = exp(-fabs(eta));
-    l = y * eta - (fmax(eta, 0.0) + log1p(e));
-    const double inv = 1.0 / (1.0 + e);
-    dl = y - (eta >= 0.0 ? inv : e * inv);
-  } else if constexpr (LIK == 3) {   // poisson_log: -inf past exp's range, no clamp
-    const double e = exp(eta);
-    l = y * eta - e;
-    dl = y - e;
-  } else {                           // neg_binomial_2_log: k0 = phi, k1 = log phi;
-    const double z = eta - k.k1;     // (y + phi) softplus(zeta), zeta = eta - log phi
-    const double e = exp(-fabs(z));
-    const double yp = y + k.k0;
-    l = y * eta - yp * (fmax(z, 0.0) + log1p(e));
-    const double inv = 1.0 / (1.0 + e);
-    dl = y - yp * (z >= 0.0 ? inv : e * inv);
-  }
-}
+constexpr bool glm_offset(int lik) { return link_has_offset(lik) || lik == 7; }
 
 __device__ __forceinline__ double glm_final_logp(const GlmK& k, double sum_l, double ss) {
   return k.c_all + (sum_l - 0.5 * k.inv_s2 * ss);
@@ -150,8 +119,8 @@ __device__ __forceinline__ void glm_link_aux(const GlmK& k, double ca, double cb
   } else if constexpr (LIK == 6) {   // t = (nu + 1) q / (nu + q^2): dl = t / sigma, dlam = t q
     const double q = (y - eta) * ca;
     const double q2 = q * q;
-    l = -k.k1 * log1p(q2 * k.inv_nu);
-    const double t = k.k2 * q / (k.nu + q2);
+    l = -k.lk.k1 * log1p(q2 * k.inv_nu);
+    const double t = k.lk.k2 * q / (k.nu + q2);
     dl = t * ca;
     dlam = t * q;
   } else {                           // phi = ca, zeta = eta - lambda
@@ -243,7 +212,7 @@ __global__ __launch_bounds__(256) void glm_rows_small_kernel(GlmK k) {
         glm_link_aux<LIK>(k, ca, cb, eta, ys[mm], l, dl, dlam);
         if constexpr (GRAD && LIK != 5) la += dlam;
       } else {
-        glm_link<LIK>(k, eta, ys[mm], l, dl);
+        obs_link<LIK>(k.lk, eta, ys[mm], l, dl);
       }
       lp += l;
       if constexpr (GRAD) {
@@ -372,9 +341,9 @@ __global__ __launch_bounds__(256) void glm_rows_mfma_kernel(GlmK k) {
           glm_link_aux<LIK>(k, rk[0], rk[1], OFFS ? eta[r] + ev : eta[r], yv, l, dl, dlam);
           if constexpr (LACC) laa[r] += ok ? dlam : 0.0;
         } else if constexpr (OFFS) {
-          glm_link<LIK>(k, eta[r] + ev, yv, l, dl);
+          obs_link<LIK>(k.lk, eta[r] + ev, yv, l, dl);
         } else {
-          glm_link<LIK>(k, eta[r], yv, l, dl);
+          obs_link<LIK>(k.lk, eta[r], yv, l, dl);
         }
         lpa[r] += ok ? l : 0.0;
         if constexpr (GRAD) Rs[(lq + 4 * r) * kGlmSR + lr] = ok ? dl : 0.0;
@@ -632,25 +601,6 @@ void glm_launch(const GlmPlan& p, const GlmK& k, hipStream_t s) {
     hipLaunchKernelGGL((glm_rows_mfma_kernel<LIK, true, 8>), g, b, 0, s, k);
 }
 
-// lgamma(x + 1/2) - lgamma(x) - log(x) / 2 for x > 0, to a few 2^-53 absolute.  The
-// difference of the two lgamma loses the digits of M c_obs as nu grows (~1e-9 per
-// observation at nu = 1e6).  From x >= 32 the asymptotic series (next term < 4e-22); a
-// smaller x climbs there by Gamma(x + 1) = x Gamma(x); below 1 the two lgamma are small
-// and their difference is taken as it stands.
-double lgamma_half_step(double x) {
-  if (x < 1.0) return std::lgamma(x + 0.5) - std::lgamma(x) - 0.5 * std::log(x);
-  const double x0 = x;
-  double steps = 0.0;
-  while (x < 32.0) {
-    steps += std::log1p(0.5 / x);
-    x += 1.0;
-  }
-  const double t = 1.0 / x, t2 = t * t;
-  const double tail =
-      t * (-1.0 / 8 + t2 * (1.0 / 192 + t2 * (-1.0 / 640 + t2 * (17.0 / 14336 + t2 * (-31.0 / 18432 + t2 * (691.0 / 180224))))));
-  return x == x0 ? tail : tail + (0.5 * std::log(x / x0) - steps);
-}
-
 }  // namespace
 
 size_t glm_scratch_doubles(int D, long long n, const GlmHead& h, bool grad) {
@@ -682,21 +632,24 @@ static hipError_t launch_glm_rows_aux(int D, long long n, const GlmHead& h, cons
   k.M = h.M;
   k.Mf = (double)h.M;
   k.chunk_obs = p.chunk_obs;
-  const double log2pi = 1.8378770664093454835606594728112;
-  double c_obs = 0.0;   // without -log sigma: -M lambda is the row's
-  if (h.lik == 0) {
-    c_obs = -0.5 * log2pi;
-  } else if (h.lik == 1) {
+  // The fixed link's constants at sigma = 1: c_obs without -log sigma (-M lambda is the
+  // row's), and the student_t's k1, k2.  Not its k0, k3, which hold sigma; and nothing of
+  // the negative binomial's, whose phi and log phi are the row's.
+  double c_obs = 0.0;
+  if (h.lik != 4) {
+    LinkK fixed;
+    c_obs = link_consts(h.lik, h.nu, 1.0, 0.0, &fixed);
+    k.lk.k1 = fixed.k1;
+    k.lk.k2 = fixed.k2;
+  }
+  if (h.lik == 1) {
     k.nu = h.nu;
     k.inv_nu = 1.0 / h.nu;
-    k.k1 = 0.5 * (h.nu + 1.0);
-    k.k2 = h.nu + 1.0;
-    c_obs = lgamma_half_step(0.5 * h.nu) - 0.5 * log2pi;
   }
   k.inv_s2 = 1.0 / (h.prior * h.prior);
   k.ls_aux = std::log(h.s_aux);
   // log(2 / (pi s_aux)): the half-Cauchy's constant
-  k.c_all = -(double)pc * (0.5 * log2pi + std::log(h.prior)) + (double)h.M * c_obs +
+  k.c_all = -(double)pc * (0.5 * kLog2Pi + std::log(h.prior)) + (double)h.M * c_obs +
             (-0.45158270528945486472619522989488 - k.ls_aux);
   if (h.lik == 4) k.c_all += h.c_data;
   k.X = params + kGlmHeader;
@@ -758,24 +711,9 @@ hipError_t launch_glm_rows(int D, long long n, const GlmHead& h, const double* p
   k.n = n;
   k.M = h.M;
   k.chunk_obs = p.chunk_obs;
-  double c_obs = 0.0;
-  const double log2pi = 1.8378770664093454835606594728112;
-  if (h.lik == 0) {
-    k.k0 = 1.0 / (h.sigma * h.sigma);
-    c_obs = -0.5 * log2pi - std::log(h.sigma);
-  } else if (h.lik == 1) {
-    k.k3 = h.nu * (h.sigma * h.sigma);
-    k.k0 = 1.0 / k.k3;
-    k.k1 = 0.5 * (h.nu + 1.0);
-    k.k2 = h.nu + 1.0;
-    // lgamma((nu + 1) / 2) - lgamma(nu / 2) - log(nu pi) / 2, the log(nu / 2) / 2 cancelled
-    c_obs = lgamma_half_step(0.5 * h.nu) - 0.5 * log2pi - std::log(h.sigma);
-  } else if (h.lik == 4) {
-    k.k0 = h.phi;
-    k.k1 = std::log(h.phi);
-  }
+  const double c_obs = link_consts(h.lik, h.nu, h.sigma, h.phi, &k.lk);
   k.inv_s2 = 1.0 / (h.prior * h.prior);
-  k.c_all = -(double)D * (0.5 * log2pi + std::log(h.prior)) + (double)h.M * c_obs;
+  k.c_all = -(double)D * (0.5 * kLog2Pi + std::log(h.prior)) + (double)h.M * c_obs;
   if (h.lik >= 3) k.c_all += h.c_data;   // the data-only constants, summed by the packer
   k.X = params + kGlmHeader;
   k.y = k.X + (size_t)h.M * D;

@@ -37,7 +37,7 @@
 //     accumulated in the chunk's partial in global memory (each lane its own row).  No
 //     matrix instructions yet.
 //
-// The links are those of vb_glm.hip's glm_link, operation for operation; the two count
+// The links are obs_link of vb_links.hpp, the definition vb_glm.hip uses; the two count
 // links (poisson_log, neg_binomial_2_log) add the block's offset eta0 [M] to eta.
 // grad == nullptr selects instances without gradient work; the value's operations are
 // the same, so it is the same bit for bit.
@@ -47,6 +47,7 @@
 #include "../../include/viabel_amd.h"
 #include "vb_device.hpp"
 #include "vb_internal.hpp"
+#include "vb_links.hpp"
 
 using namespace vbd;
 
@@ -63,7 +64,7 @@ constexpr long long kMlmScratchMax = 32LL << 20;          // doubles of chunk pa
 struct MlmK {
   int p, G, D, nchunk, centered;
   long long n, M, chunk_obs;
-  double k0, k1, k2, k3;          // link constants (mlm_link)
+  LinkK lk;                       // link constants (vb_links.hpp)
   double inv_s2, inv_stau, c_all; // prior precision, 1 / s_tau, every constant of log p
   const double* X;                // [M][p]
   const double* y;                // [M]
@@ -79,38 +80,6 @@ struct MlmK {
   double* pg;                     // [nchunk][n][p] (grad)
   const double* eta0;             // [M]: offset of eta (LIK >= 3; not read otherwise)
 };
-
-// l(y, eta) without its constant, and dl / d eta (glm_link of vb_glm.hip)
-template <int LIK>
-__device__ __forceinline__ void mlm_link(const MlmK& k, double eta, double y, double& l,
-                                         double& dl) {
-  if constexpr (LIK == 0) {          // gaussian: k0 = 1 / sigma^2
-    const double r = y - eta;
-    l = -0.5 * k.k0 * (r * r);
-    dl = k.k0 * r;
-  } else if constexpr (LIK == 1) {   // student_t: k0 = 1 / (nu sigma^2), k1 = (nu + 1) / 2,
-    const double r = y - eta;        //            k2 = nu + 1, k3 = nu sigma^2
-    const double r2 = r * r;
-    l = -k.k1 * log1p(r2 * k.k0);
-    dl = k.k2 * r / (k.k3 + r2);
-  } else if constexpr (LIK == 2) {   // bernoulli_logit: softplus and the logistic from one exp
-    const double e = exp(-fabs(eta));
-    l = y * eta - (fmax(eta, 0.0) + log1p(e));
-    const double inv = 1.0 / (1.0 + e);
-    dl = y - (eta >= 0.0 ? inv : e * inv);
-  } else if constexpr (LIK == 3) {   // poisson_log: -inf past exp's range, no clamp
-    const double e = exp(eta);
-    l = y * eta - e;
-    dl = y - e;
-  } else {                           // neg_binomial_2_log: k0 = phi, k1 = log phi;
-    const double z = eta - k.k1;     // (y + phi) softplus(zeta), zeta = eta - log phi
-    const double e = exp(-fabs(z));
-    const double yp = y + k.k0;
-    l = y * eta - yp * (fmax(z, 0.0) + log1p(e));
-    const double inv = 1.0 / (1.0 + e);
-    dl = y - yp * (z >= 0.0 ? inv : e * inv);
-  }
-}
 
 // The group g with off[g] <= m < off[g + 1], searched from lo (off[lo] <= m); the
 // result lies in [lo, G - 1] whatever off holds.
@@ -186,7 +155,7 @@ __device__ __forceinline__ void mlm_store_partials(const MlmK& k, const MlmWalk&
 template <int LIK, bool GRAD, int PP>
 __global__ __launch_bounds__(256) void mlm_rows_lane_kernel(MlmK k) {
   __shared__ double Xs[kMlmTile * PP];
-  constexpr bool OFFS = LIK >= 3;               // eta0 rides behind y in the tile
+  constexpr bool OFFS = link_has_offset(LIK);   // eta0 rides behind y in the tile
   __shared__ double ys[OFFS ? 2 * kMlmTile : kMlmTile];
   __shared__ int gs[kMlmTile];
   const int t = threadIdx.x, nt = blockDim.x, p = k.p, G = k.G;
@@ -238,7 +207,7 @@ __global__ __launch_bounds__(256) void mlm_rows_lane_kernel(MlmK k) {
       for (int d = 0; d < PP; ++d) eta = fma(beta[d], xm[d], eta);
       if constexpr (OFFS) eta += ys[kMlmTile + mm];
       double l, dl;
-      mlm_link<LIK>(k, eta, ys[mm], l, dl);
+      obs_link<LIK>(k.lk, eta, ys[mm], l, dl);
       lp += l;
       if constexpr (GRAD) {
         w.S += dl;
@@ -263,7 +232,7 @@ __global__ __launch_bounds__(256) void mlm_rows_lane_kernel(MlmK k) {
 template <int LIK, bool GRAD>
 __global__ __launch_bounds__(64) void mlm_rows_tile_kernel(MlmK k) {
   __shared__ double Xs[kMlmTM * kMlmKS];
-  constexpr bool OFFS = LIK >= 3;               // eta0 rides behind y
+  constexpr bool OFFS = link_has_offset(LIK);   // eta0 rides behind y
   __shared__ double ys[OFFS ? 2 * kMlmTM : kMlmTM];
   __shared__ int gs[kMlmTM];
   const int t = threadIdx.x, p = k.p, G = k.G;
@@ -326,9 +295,9 @@ __global__ __launch_bounds__(64) void mlm_rows_tile_kernel(MlmK k) {
         mlm_enter<GRAD>(k, w, gs[mm], gfirst, glast, tau, it, ar, gr, live);
         double l, dl;
         if constexpr (OFFS)
-          mlm_link<LIK>(k, (eta[mm] + w.aeff) + ys[kMlmTM + mm], ys[mm], l, dl);
+          obs_link<LIK>(k.lk, (eta[mm] + w.aeff) + ys[kMlmTM + mm], ys[mm], l, dl);
         else
-          mlm_link<LIK>(k, eta[mm] + w.aeff, ys[mm], l, dl);
+          obs_link<LIK>(k.lk, eta[mm] + w.aeff, ys[mm], l, dl);
         lp += l;
         if constexpr (GRAD) {
           w.S += dl;
@@ -501,23 +470,6 @@ void mlm_launch(const MlmPlan& pl, const MlmK& k, hipStream_t s) {
     hipLaunchKernelGGL((mlm_rows_lane_kernel<LIK, GRAD, 16>), g, b, 0, s, k);
 }
 
-// lgamma(x + 1/2) - lgamma(x) - log(x) / 2 for x > 0 to a few 2^-53 absolute, as
-// vb_glm.hip forms the Student-t constant: the asymptotic series from x >= 32, a smaller
-// x climbing there by Gamma(x + 1) = x Gamma(x), the two lgamma as they stand below 1.
-double mlm_lgamma_half_step(double x) {
-  if (x < 1.0) return std::lgamma(x + 0.5) - std::lgamma(x) - 0.5 * std::log(x);
-  const double x0 = x;
-  double steps = 0.0;
-  while (x < 32.0) {
-    steps += std::log1p(0.5 / x);
-    x += 1.0;
-  }
-  const double t = 1.0 / x, t2 = t * t;
-  const double tail =
-      t * (-1.0 / 8 + t2 * (1.0 / 192 + t2 * (-1.0 / 640 + t2 * (17.0 / 14336 + t2 * (-31.0 / 18432 + t2 * (691.0 / 180224))))));
-  return x == x0 ? tail : tail + (0.5 * std::log(x / x0) - steps);
-}
-
 }  // namespace
 
 size_t mlm_scratch_doubles(int D, long long n, const MlmHead& h, bool grad) {
@@ -547,27 +499,12 @@ hipError_t launch_mlm_rows(int D, long long n, const MlmHead& h, const double* p
   k.n = n;
   k.M = h.M;
   k.chunk_obs = pl.chunk_obs;
-  double c_obs = 0.0;
-  const double log2pi = 1.8378770664093454835606594728112;
-  if (h.lik == 0) {
-    k.k0 = 1.0 / (h.sigma * h.sigma);
-    c_obs = -0.5 * log2pi - std::log(h.sigma);
-  } else if (h.lik == 1) {
-    k.k3 = h.nu * (h.sigma * h.sigma);
-    k.k0 = 1.0 / k.k3;
-    k.k1 = 0.5 * (h.nu + 1.0);
-    k.k2 = h.nu + 1.0;
-    // lgamma((nu + 1) / 2) - lgamma(nu / 2) - log(nu pi) / 2, the log(nu / 2) / 2 cancelled
-    c_obs = mlm_lgamma_half_step(0.5 * h.nu) - 0.5 * log2pi - std::log(h.sigma);
-  } else if (h.lik == 4) {
-    k.k0 = h.phi;
-    k.k1 = std::log(h.phi);
-  }
+  const double c_obs = link_consts(h.lik, h.nu, h.sigma, h.phi, &k.lk);
   k.inv_s2 = 1.0 / (h.prior * h.prior);
   k.inv_stau = 1.0 / h.tau_scale;
   // beta's prior, the observations, the half-Cauchy log(2 / (pi s_tau)), the groups' normal
-  k.c_all = -(double)p * (0.5 * log2pi + std::log(h.prior)) + (double)h.M * c_obs +
-            (std::log(2.0 / M_PI) - std::log(h.tau_scale)) - (double)h.G * (0.5 * log2pi);
+  k.c_all = -(double)p * (0.5 * kLog2Pi + std::log(h.prior)) + (double)h.M * c_obs +
+            (std::log(2.0 / M_PI) - std::log(h.tau_scale)) - (double)h.G * (0.5 * kLog2Pi);
   if (h.lik >= 3) k.c_all += h.c_data;   // the data-only constants, summed by the packer
   k.X = params + kMlmHeader;
   k.y = k.X + (size_t)h.M * p;

@@ -286,6 +286,60 @@ def _check_counts(likelihood, y, offset, phi, m, learn_phi=False):
     return offset
 
 
+def _check_likelihood(likelihood):
+    if likelihood not in _LIKELIHOODS:
+        raise ValueError('unknown likelihood %r (expected one of %s)'
+                         % (likelihood, ', '.join(sorted(_LIKELIHOODS))))
+
+
+def _check_design_shape(x, y, dims):
+    """The shape checks shared by regression and multilevel_regression (dims: how the
+    message names x's shape); returns x and y as float64 arrays."""
+    x = np.asarray(x, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    if x.ndim != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError('x must be a non-empty %s matrix, got shape %s' % (dims, x.shape))
+    if y.shape != (x.shape[0],):
+        raise ValueError('y must have shape (%d,), got %s' % (x.shape[0], y.shape))
+    return x, y
+
+
+def _check_design(x, y, likelihood, df, scale, prior_scale, tau_scale=None, learn_scale=False):
+    """The value checks shared by regression and multilevel_regression, after the shape
+    checks (and, in the multilevel target, the group checks between the two); tau_scale
+    is the multilevel target's, learn_scale says that `scale` is not used.  Returns whether
+    the likelihood is a count likelihood."""
+    if not (np.all(np.isfinite(x)) and np.all(np.isfinite(y))):
+        raise ValueError('x and y must be finite')
+    if not (np.isfinite(prior_scale) and prior_scale > 0):
+        raise ValueError('prior_scale must be positive')
+    if tau_scale is not None and not (np.isfinite(tau_scale) and tau_scale > 0):
+        raise ValueError('tau_scale must be positive')
+    if likelihood == 'student_t':
+        if df is None or not (np.isfinite(df) and df > 0):
+            raise ValueError('the student_t likelihood needs df > 0')
+    if likelihood in ('gaussian', 'student_t'):
+        if not learn_scale and not (np.isfinite(scale) and scale > 0):
+            raise ValueError('scale must be positive')
+    elif likelihood == 'bernoulli_logit' and not np.all((y == 0) | (y == 1)):
+        raise ValueError('the bernoulli_logit likelihood needs y in {0, 1}')
+    return likelihood in _COUNT_LIKELIHOODS
+
+
+def _fill_link_params(params, likelihood, m, df, phi, scale, prior_scale):
+    """params[0..4] of a regression or multilevel block (include/viabel_amd.h); phi / scale
+    None: learned, the slot stays 0."""
+    params[0] = _LIKELIHOODS[likelihood]
+    params[1] = m
+    if likelihood == 'student_t':
+        params[2] = df
+    elif likelihood == 'neg_binomial_2_log' and phi is not None:
+        params[2] = phi
+    if likelihood in ('gaussian', 'student_t') and scale is not None:
+        params[3] = scale
+    params[4] = prior_scale
+
+
 def regression(x, y, likelihood='student_t', df=None, scale=1.0, prior_scale=10.0, offset=None,
                phi=None, learn_scale=False, learn_phi=False, hyper_scale=5.0):
     """A generalised linear model evaluated on the device: beta_d ~ N(0,
@@ -309,9 +363,7 @@ def regression(x, y, likelihood='student_t', df=None, scale=1.0, prior_scale=10.
     log sigma, or lambda = log phi, with e^lambda ~ half-Cauchy(0, hyper_scale) and the
     Jacobian of the log kept.  Such a target carries n_coef = p and learned = 'scale' or
     'phi'; learn_phi needs max(y) <= 65536."""
-    if likelihood not in _LIKELIHOODS:
-        raise ValueError('unknown likelihood %r (expected one of %s)'
-                         % (likelihood, ', '.join(sorted(_LIKELIHOODS))))
+    _check_likelihood(likelihood)
     if learn_scale and likelihood not in ('gaussian', 'student_t'):
         raise ValueError('learn_scale=True is valid for the gaussian and student_t likelihoods '
                          'only, not for %r' % (likelihood,))
@@ -321,26 +373,8 @@ def regression(x, y, likelihood='student_t', df=None, scale=1.0, prior_scale=10.
     learn = bool(learn_scale or learn_phi)
     if learn and not (np.isfinite(hyper_scale) and hyper_scale > 0):
         raise ValueError('hyper_scale must be positive')
-    x = np.asarray(x, dtype=np.float64)
-    y = np.asarray(y, dtype=np.float64)
-    if x.ndim != 2 or x.shape[0] < 1 or x.shape[1] < 1:
-        raise ValueError('x must be a non-empty (M, D) matrix, got shape %s' % (x.shape,))
-    if y.shape != (x.shape[0],):
-        raise ValueError('y must have shape (%d,), got %s' % (x.shape[0], y.shape))
-    if not (np.all(np.isfinite(x)) and np.all(np.isfinite(y))):
-        raise ValueError('x and y must be finite')
-    if not (np.isfinite(prior_scale) and prior_scale > 0):
-        raise ValueError('prior_scale must be positive')
-    if likelihood == 'student_t':
-        if df is None or not (np.isfinite(df) and df > 0):
-            raise ValueError('the student_t likelihood needs df > 0')
-    count = likelihood in _COUNT_LIKELIHOODS
-    located = likelihood in ('gaussian', 'student_t')
-    if located:
-        if not learn_scale and not (np.isfinite(scale) and scale > 0):
-            raise ValueError('scale must be positive')
-    elif likelihood == 'bernoulli_logit' and not np.all((y == 0) | (y == 1)):
-        raise ValueError('the bernoulli_logit likelihood needs y in {0, 1}')
+    x, y = _check_design_shape(x, y, '(M, D)')
+    count = _check_design(x, y, likelihood, df, scale, prior_scale, learn_scale=learn_scale)
     m, d = x.shape
     offset = _check_counts(likelihood, y, offset, phi, m, learn_phi)
     table = None
@@ -353,12 +387,7 @@ def regression(x, y, likelihood='student_t', df=None, scale=1.0, prior_scale=10.
     h = REGRESSION_HEADER
     params = np.zeros(h + m * d + m + (m + 1 if count else 0)
                       + (1 + table.size if table is not None else 0))
-    params[0] = _LIKELIHOODS[likelihood]
-    params[1] = m
-    params[2] = (df if likelihood == 'student_t'
-                 else phi if likelihood == 'neg_binomial_2_log' and not learn_phi else 0.0)
-    params[3] = scale if located and not learn_scale else 0.0
-    params[4] = prior_scale
+    _fill_link_params(params, likelihood, m, df, phi, None if learn_scale else scale, prior_scale)
     if learn:
         params[5] = 1.0
         params[6] = hyper_scale
@@ -489,16 +518,9 @@ def multilevel_regression(x, y, group, likelihood='gaussian', df=None, scale=1.0
     kept as `order`) and packed with the group offsets into one parameter array
     (layout in include/viabel_amd.h) that the library uploads per run, so no host call
     happens inside a fit."""
-    if likelihood not in _LIKELIHOODS:
-        raise ValueError('unknown likelihood %r (expected one of %s)'
-                         % (likelihood, ', '.join(sorted(_LIKELIHOODS))))
-    x = np.asarray(x, dtype=np.float64)
-    y = np.asarray(y, dtype=np.float64)
-    if x.ndim != 2 or x.shape[0] < 1 or x.shape[1] < 1:
-        raise ValueError('x must be a non-empty (M, p) matrix, got shape %s' % (x.shape,))
+    _check_likelihood(likelihood)
+    x, y = _check_design_shape(x, y, '(M, p)')
     m, p = x.shape
-    if y.shape != (m,):
-        raise ValueError('y must have shape (%d,), got %s' % (m, y.shape))
     graw = np.asarray(group)
     if graw.shape != (m,):
         raise ValueError('group must have shape (%d,), got %s' % (m, graw.shape))
@@ -518,32 +540,13 @@ def multilevel_regression(x, y, group, likelihood='gaussian', df=None, scale=1.0
     n_groups = int(n_groups)
     if int(g.max()) >= n_groups:
         raise ValueError('group label %d is not below n_groups = %d' % (int(g.max()), n_groups))
-    if not (np.all(np.isfinite(x)) and np.all(np.isfinite(y))):
-        raise ValueError('x and y must be finite')
-    if not (np.isfinite(prior_scale) and prior_scale > 0):
-        raise ValueError('prior_scale must be positive')
-    if not (np.isfinite(tau_scale) and tau_scale > 0):
-        raise ValueError('tau_scale must be positive')
-    if likelihood == 'student_t':
-        if df is None or not (np.isfinite(df) and df > 0):
-            raise ValueError('the student_t likelihood needs df > 0')
-    count = likelihood in _COUNT_LIKELIHOODS
-    located = likelihood in ('gaussian', 'student_t')
-    if located:
-        if not (np.isfinite(scale) and scale > 0):
-            raise ValueError('scale must be positive')
-    elif likelihood == 'bernoulli_logit' and not np.all((y == 0) | (y == 1)):
-        raise ValueError('the bernoulli_logit likelihood needs y in {0, 1}')
+    count = _check_design(x, y, likelihood, df, scale, prior_scale, tau_scale=tau_scale)
     offset = _check_counts(likelihood, y, offset, phi, m)
     order = np.argsort(g, kind='stable')
     offsets = np.concatenate([[0], np.cumsum(np.bincount(g, minlength=n_groups))])
     h = MULTILEVEL_HEADER
     params = np.zeros(h + m * p + m + n_groups + 1 + (m + 1 if count else 0))
-    params[0] = _LIKELIHOODS[likelihood]
-    params[1] = m
-    params[2] = df if likelihood == 'student_t' else phi if likelihood == 'neg_binomial_2_log' else 0.0
-    params[3] = scale if located else 0.0
-    params[4] = prior_scale
+    _fill_link_params(params, likelihood, m, df, phi, scale, prior_scale)
     params[5] = n_groups
     params[6] = tau_scale
     params[7] = 1.0 if centered else 0.0
