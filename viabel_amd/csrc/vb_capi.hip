@@ -787,14 +787,6 @@ int multilevel_head(const vb_target* t, vbk::MlmHead* o) {
   return VB_OK;
 }
 
-// Host copies of the headers of the targets that carry a parameter block.
-struct TargetHeads {
-  vbk::GlmHead glm{};
-  vbk::HierHead hier{};
-  vbk::MlmHead mlm{};
-  vbk::PluginTarget plugin{};
-};
-
 // Whether the target's `params` is a block used whole (regression, hierarchical,
 // multilevel, and a plugin's data block, which may be absent).
 bool block_target(int kind) {
@@ -802,7 +794,12 @@ bool block_target(int kind) {
          kind == VB_TARGET_MULTILEVEL || kind == VB_TARGET_PLUGIN;
 }
 
-int check_target(const vb_target* t, int D, TargetHeads* heads = nullptr) {
+// Checks a vb_target against the family dimension D and fills the launch functions' view
+// of it (out nullable): kind, D, block length and the kind's own header.  Its device
+// pointer and log normaliser come from stage_target.
+int check_target(const vb_target* t, int D, vbk::Target* out = nullptr) {
+  vbk::Target unused;
+  vbk::Target& o = out ? *out : unused;
   if (!t) return fail(VB_EINVAL, "null vb_target");
   if (t->kind < VB_TARGET_ISOGAUSS || t->kind > VB_TARGET_PLUGIN)
     return fail(VB_EUNSUPPORTED, "target kind %d is not implemented on the device", t->kind);
@@ -817,31 +814,37 @@ int check_target(const vb_target* t, int D, TargetHeads* heads = nullptr) {
   if (t->kind == VB_TARGET_FUNNEL && D < 2) return fail(VB_EINVAL, "funnel target needs D >= 2");
   if (t->kind == VB_TARGET_EIGHT_SCHOOLS_NCP && D != 10)
     return fail(VB_EINVAL, "eight_schools_ncp target has dimension 10, got %d", D);
-  if (t->kind == VB_TARGET_REGRESSION) {
-    vbk::GlmHead h{};
-    VB_TRY(regression_head(t, &h));
-    if (heads) heads->glm = h;
-  }
-  if (t->kind == VB_TARGET_HIERARCHICAL) {
-    vbk::HierHead h{};
-    VB_TRY(hierarchical_head(t, &h));
-    if (heads) heads->hier = h;
-  }
-  if (t->kind == VB_TARGET_MULTILEVEL) {
-    vbk::MlmHead h{};
-    VB_TRY(multilevel_head(t, &h));
-    if (heads) heads->mlm = h;
-  }
-  if (t->kind == VB_TARGET_PLUGIN) {
-    if (t->callback) return fail(VB_EINVAL, "plugin target: callback must be null");
-    if (t->n_params < 0 || (t->n_params > 0 && !t->params) || (t->n_params == 0 && t->params))
-      return fail(VB_EINVAL, "plugin target: params / n_params must be a data block, or null and 0");
-    if (ptr_class(t->params) < 0) return foreign_ptr_error(t->params);
-    int dev = 0;
-    VB_HIP(hipGetDevice(&dev));   // the context's: entry points select it first
-    vbk::PluginTarget p{};
-    VB_TRY(vbk::plugin_view(static_cast<const vb_plugin*>(t->user), dev, t->dim, t->n_params, &p));
-    if (heads) heads->plugin = p;
+  o = vbk::Target();
+  o.kind = t->kind;
+  o.D = D;
+  o.n_params = (long long)t->n_params;
+  switch (t->kind) {
+    case VB_TARGET_CALLBACK:
+      o.host = vbk::HostTarget{t->callback, t->user};
+      break;
+    case VB_TARGET_REGRESSION:
+      VB_TRY(regression_head(t, &o.glm));
+      break;
+    case VB_TARGET_HIERARCHICAL:
+      VB_TRY(hierarchical_head(t, &o.hier));
+      break;
+    case VB_TARGET_MULTILEVEL:
+      VB_TRY(multilevel_head(t, &o.mlm));
+      break;
+    case VB_TARGET_PLUGIN: {
+      if (t->callback) return fail(VB_EINVAL, "plugin target: callback must be null");
+      if (t->n_params < 0 || (t->n_params > 0 && !t->params) || (t->n_params == 0 && t->params))
+        return fail(VB_EINVAL, "plugin target: params / n_params must be a data block, or null and 0");
+      if (ptr_class(t->params) < 0) return foreign_ptr_error(t->params);
+      int dev = 0;
+      VB_HIP(hipGetDevice(&dev));   // the context's: entry points select it first
+      o.plugin = vbk::PluginTarget{};
+      VB_TRY(vbk::plugin_view(static_cast<const vb_plugin*>(t->user), dev, t->dim, t->n_params,
+                              &o.plugin));
+      break;
+    }
+    default:
+      break;
   }
   return VB_OK;
 }
@@ -853,29 +856,23 @@ vbk::Noise noise_of(const vb_noise* n, const double* eps) {
                     n->stream_stride ? n->stream_stride : 1u, (long long)n->step};
 }
 
-// Context slots that target_params stages into.  Each stays clear of the slots its
-// entry points stage arguments and scratch in:
-constexpr int kSlotRunTparams = 1;  // vb_run_create: copied into the run; init then takes 0
-constexpr int kSlotTparams = 3;     // corr_gauss: lam, draws, gradient in 0-2, the value in 4
-constexpr int kSlotTparamsLw = 4;   // corr_gauss in vb_log_weights, whose samples take 3
-constexpr int kSlotGlm = 8;         // parameter block (block_target): the mean-field calls use 0-7
+// The context slot that stage_target stages into: the entry points stage their own
+// arguments and scratch in the slots 0-7.
+constexpr int kSlotTarget = 8;
 
-// Device copy of a target's parameters and its scalar log normaliser.
-int target_params(vb_ctx* c, int s, const vb_target* t, const double** dev, double* tconst) {
-  *dev = nullptr;
-  *tconst = 0.0;
-  if (block_target(t->kind)) {   // the whole block; a device pointer is used in place
-    In in;
-    VB_TRY(in.stage(c, s, t->params, (size_t)t->n_params));
-    *dev = in.d;
-    return VB_OK;
-  }
-  if (t->kind != VB_TARGET_CORR_GAUSS) return VB_OK;
-  const size_t dd = (size_t)t->dim * t->dim;
+// Device copy of a checked target's parameters (a device pointer is used in place) and,
+// for corr_gauss, its log normaliser: the block's last value.
+int stage_target(vb_ctx* c, const vb_target* t, vbk::Target* o) {
+  o->params = nullptr;
+  o->tconst = 0.0;
+  const bool corr = t->kind == VB_TARGET_CORR_GAUSS;   // P* [D][D], then the normaliser
+  if (!corr && !block_target(t->kind)) return VB_OK;
   In in;
-  VB_TRY(in.stage(c, s, t->params, dd + 1));
-  *dev = in.d;
-  VB_HIP(hipMemcpyAsync(tconst, in.d + dd, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  VB_TRY(in.stage(c, kSlotTarget, t->params, (size_t)t->n_params));
+  o->params = in.d;
+  if (!corr) return VB_OK;
+  VB_HIP(hipMemcpyAsync(&o->tconst, in.d + (t->n_params - 1), sizeof(double), hipMemcpyDeviceToHost,
+                        c->stream));
   VB_HIP(hipStreamSynchronize(c->stream));
   return VB_OK;
 }
@@ -944,32 +941,15 @@ int choose_path(const PathFacts& f, Path* out) {
   return VB_OK;
 }
 
-vbk::HostTarget host_of(const vb_target* t) {
-  vbk::HostTarget h{};
-  if (t && t->kind == VB_TARGET_CALLBACK) {
-    h.fn = t->callback;
-    h.user = t->user;
-  }
-  return h;
-}
-
 // obj null: log weights (no sample count, no objective flags)
-vbk::Spec make_spec(const FamInfo& fi, const vb_target* tgt, const vb_objective* obj,
-                    const double* tparams, double tconst, const TargetHeads& heads) {
+vbk::Spec make_spec(const FamInfo& fi, const vbk::Target& target, const vb_objective* obj) {
   vbk::Spec f{};
   f.fam = fi;
   f.N = obj ? (int)obj->n_samples : 0;
-  f.tgt = tgt->kind;
   f.chivi = obj && obj->kind == VB_OBJ_CHIVI;
   f.pd = obj && obj->kind == VB_OBJ_KLVI_PD;
   f.alpha = obj ? obj->alpha : 2.0;
-  f.tparams = tparams;
-  f.tconst = tconst;
-  f.host = host_of(tgt);
-  f.glm = heads.glm;
-  f.hier = heads.hier;
-  f.mlm = heads.mlm;
-  f.plugin = heads.plugin;
+  f.tgt = target;
   return f;
 }
 
@@ -993,7 +973,7 @@ double sep_c0(const FamInfo& fi, bool pd) {
 // vb_objective_value_grad for the full-rank families
 int fr_objective(vb_ctx* c, const FamInfo& fi, const vb_target* tgt, const vb_objective* obj,
                  const double* lam, const vb_noise* noise, double* value, double* grad,
-                 const TargetHeads& heads) {
+                 vbk::Target& target) {
   const bool host = noise->kind == VB_NOISE_HOST;
   if (host && !noise->eps) return fail(VB_EINVAL, "host noise requires eps");
   const size_t N = (size_t)obj->n_samples;
@@ -1003,15 +983,12 @@ int fr_objective(vb_ctx* c, const FamInfo& fi, const vb_target* tgt, const vb_ob
   const bool gauss = fi.kind == VB_FAMILY_FR_GAUSSIAN;   // draws are z alone, no scale s
   if (host) VB_TRY(dn.stage(c, 1, noise->eps, N * vbk::family_noise_width(fi)));
   VB_TRY(dg.stage(c, 2, grad, fi.P));
-  const double* tp;
-  double tc;
-  VB_TRY(target_params(c, block_target(tgt->kind) ? kSlotGlm : kSlotTparams, tgt, &tp,
-                       &tc));
+  VB_TRY(stage_target(c, tgt, &target));
   VB_TRY(c->slot[4].reserve(sizeof(double) * 2));
   vbk::FrWork* W;
   VB_TRY(fr_work(c, &W));
   if (gauss || fi.kind == VB_FAMILY_LR_GAUSSIAN) {
-    const vbk::Spec f = make_spec(fi, tgt, obj, tp, tc, heads);
+    const vbk::Spec f = make_spec(fi, target, obj);
     const vbk::Noise nz = noise_of(noise, host ? dn.d : nullptr);
     if (gauss)
       VB_TRY(vbk::frg_value_grad(W, f, dl.d, nz, c->slot[4].d(), dg.d, c->stream));
@@ -1024,7 +1001,7 @@ int fr_objective(vb_ctx* c, const FamInfo& fi, const vb_target* tgt, const vb_ob
   // a root or gradient solve that needed more iterations than launched (an
   // ill-conditioned Sigma) runs the call again with larger counts (fr_info)
   for (int attempt = 0;; ++attempt) {
-    VB_TRY(vbk::fr_value_grad(W, make_spec(fi, tgt, obj, tp, tc, heads), dl.d,
+    VB_TRY(vbk::fr_value_grad(W, make_spec(fi, target, obj), dl.d,
                               noise_of(noise, host ? dn.d : nullptr), c->slot[4].d(), dg.d,
                               c->stream));
     VB_TRY(sync(c));
@@ -1285,59 +1262,19 @@ int vb_target_logdensity(vb_ctx* c, const vb_target* tgt, const double* x, int64
                          double* out, double* grad_out) {
   VB_TRY(check_ctx(c));
   if (!tgt) return fail(VB_EINVAL, "null target");
-  TargetHeads heads;
-  VB_TRY(check_target(tgt, (int)tgt->dim, &heads));
+  vbk::Target target;
+  VB_TRY(check_target(tgt, (int)tgt->dim, &target));
   if (!x || !out || n < 0) return fail(VB_EINVAL, "null argument");
-  const int D = (int)tgt->dim;
   In dxx;
   Out dout, dg;
-  VB_TRY(dxx.stage(c, 0, x, (size_t)n * D));
+  VB_TRY(dxx.stage(c, 0, x, (size_t)n * target.D));
   VB_TRY(dout.stage(c, 1, out, (size_t)n));
-  VB_TRY(dg.stage(c, 2, grad_out, grad_out ? (size_t)n * D : 0));
-  if (tgt->kind == VB_TARGET_CALLBACK) {
-    if (n == 0) return VB_OK;
-    vbk::FrWork* W;
-    VB_TRY(fr_work(c, &W));
-    VB_TRY(vbk::host_target_eval(W, host_of(tgt), D, n, dxx.d, dout.d, dg.d, c->stream));
-  } else if (tgt->kind == VB_TARGET_REGRESSION) {
-    if (n == 0) return VB_OK;
-    const double* tp;
-    double tc;
-    VB_TRY(target_params(c, kSlotGlm, tgt, &tp, &tc));
-    vbk::FrWork* W;
-    VB_TRY(fr_work(c, &W));
-    VB_TRY(vbk::glm_target_eval(W, heads.glm, D, n, tp, dxx.d, dout.d, dg.d, c->stream));
-  } else if (tgt->kind == VB_TARGET_HIERARCHICAL) {
-    if (n == 0) return VB_OK;
-    const double* tp;
-    double tc;
-    VB_TRY(target_params(c, kSlotGlm, tgt, &tp, &tc));
-    VB_HIP(vbk::launch_hier_rows(D, n, heads.hier, tp, dxx.d, dout.d, dg.d, c->stream));
-  } else if (tgt->kind == VB_TARGET_MULTILEVEL) {
-    if (n == 0) return VB_OK;
-    const double* tp;
-    double tc;
-    VB_TRY(target_params(c, kSlotGlm, tgt, &tp, &tc));
-    vbk::FrWork* W;
-    VB_TRY(fr_work(c, &W));
-    VB_TRY(vbk::mlm_target_eval(W, heads.mlm, D, n, tp, dxx.d, dout.d, dg.d, c->stream));
-  } else if (tgt->kind == VB_TARGET_PLUGIN) {
-    if (n == 0) return VB_OK;
-    const double* tp;
-    double tc;
-    VB_TRY(target_params(c, kSlotGlm, tgt, &tp, &tc));
-    VB_TRY(vbk::plugin_target_eval(heads.plugin, D, n, tp, dxx.d, dout.d, dg.d, c->stream));
-  } else if (tgt->kind == VB_TARGET_CORR_GAUSS) {
-    if (n == 0) return VB_OK;
-    const double* tp;
-    double tc;
-    VB_TRY(target_params(c, kSlotTparams, tgt, &tp, &tc));
-    vbk::FrWork* W;
-    VB_TRY(fr_work(c, &W));
-    VB_TRY(vbk::fr_target(W, tgt->kind, D, n, tp, tc, dxx.d, dout.d, dg.d, c->stream));
-  } else {
-    VB_HIP(vbk::launch_target_logdensity(tgt->kind, D, n, dxx.d, dout.d, dg.d, c->stream));
-  }
+  VB_TRY(dg.stage(c, 2, grad_out, grad_out ? (size_t)n * target.D : 0));
+  if (n == 0) return VB_OK;
+  VB_TRY(stage_target(c, tgt, &target));
+  vbk::FrWork* W;
+  VB_TRY(fr_work(c, &W));
+  VB_TRY(vbk::target_eval(W, target, n, dxx.d, dout.d, dg.d, c->stream));
   VB_TRY(dout.finish(c));
   VB_TRY(dg.finish(c));
   return sync(c);
@@ -1350,15 +1287,15 @@ int vb_objective_value_grad(vb_ctx* c, const vb_family* fam, const vb_target* tg
   VB_TRY(check_ctx(c));
   FamInfo fi;
   VB_TRY(check_family(fam, &fi));
-  TargetHeads heads;
-  VB_TRY(check_target(tgt, fi.D, &heads));
+  vbk::Target target;
+  VB_TRY(check_target(tgt, fi.D, &target));
   if (!obj || !lam || !noise || !value || !grad) return fail(VB_EINVAL, "null argument");
   VB_TRY(check_objective(obj));
   if (obj->kind == VB_OBJ_CHIVI && !(obj->alpha > 0))
     return fail(VB_EINVAL, "alpha must be positive");
   Path path;
   VB_TRY(choose_path({fi.kind, tgt->kind, fi.D, obj->kind}, &path));
-  if (family_path(path)) return fr_objective(c, fi, tgt, obj, lam, noise, value, grad, heads);
+  if (family_path(path)) return fr_objective(c, fi, tgt, obj, lam, noise, value, grad, target);
   const int D = fi.D, N = (int)obj->n_samples;
   const size_t P = 2 * (size_t)D;
   const bool host = noise->kind == VB_NOISE_HOST;
@@ -1421,13 +1358,11 @@ int vb_objective_value_grad(vb_ctx* c, const vb_family* fam, const vb_target* tg
     }
     default: {
       // CHIVI or a non-separable target at D > kBlockDMax, a callback or a parameter block
-      const double* tp;
-      double tc;
-      VB_TRY(target_params(c, kSlotGlm, tgt, &tp, &tc));
+      VB_TRY(stage_target(c, tgt, &target));
       vbk::FrWork* W;
       VB_TRY(fr_work(c, &W));
-      VB_TRY(vbk::mf_wide_value_grad(W, make_spec(fi, tgt, obj, tp, tc, heads), c->slot[3].d(), nz, dval,
-                                     dg.d, c->stream));
+      VB_TRY(vbk::mf_wide_value_grad(W, make_spec(fi, target, obj), c->slot[3].d(), nz, dval, dg.d,
+                                     c->stream));
     }
   }
   VB_HIP(hipMemcpyAsync(value, dval, sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -1538,8 +1473,8 @@ int vb_run_create(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const v
   *out = nullptr;
   FamInfo fi;
   VB_TRY(check_family(fam, &fi));
-  TargetHeads heads;
-  VB_TRY(check_target(tgt, fi.D, &heads));
+  vbk::Target target;
+  VB_TRY(check_target(tgt, fi.D, &target));
   VB_TRY(check_pairing(fi.kind, tgt->kind));  // reported before the argument errors below
   if (!obj || !cfg || !init) return fail(VB_EINVAL, "null argument");
   if (!(cfg->learning_rate > 0)) return fail(VB_EINVAL, "learning rate must be positive");
@@ -1588,23 +1523,17 @@ int vb_run_create(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const v
   int rc;
   // the target's parameter block is copied once into the run; its steps read it from
   // there (the caller's pointer is not kept)
-  const double* run_tp = nullptr;
-  double tc = 0.0;
-  if (fr || (wide && block_target(tgt->kind))) {
-    const double* tp;
-    if ((rc = target_params(c, kSlotRunTparams, tgt, &tp, &tc)) != VB_OK) return bail(rc);
-    run_tp = tp;
-    if (tp) {
-      const size_t np = (size_t)tgt->n_params;
-      if ((rc = r->tparams.reserve(sizeof(double) * np)) != VB_OK) return bail(rc);
-      hipError_t e = hipMemcpyAsync(r->tparams.p, tp, sizeof(double) * np, hipMemcpyDeviceToDevice,
-                                    c->stream);
-      if (e != hipSuccess) return bail(fail(VB_EDEVICE, "hipMemcpy failed: %s", hipGetErrorString(e)));
-      run_tp = r->tparams.d();
-    }
-  }
   if (fr || wide) {
-    r->spec = make_spec(fi, tgt, obj, run_tp, tc, heads);
+    if ((rc = stage_target(c, tgt, &target)) != VB_OK) return bail(rc);
+    if (target.params) {
+      const size_t np = (size_t)target.n_params;
+      if ((rc = r->tparams.reserve(sizeof(double) * np)) != VB_OK) return bail(rc);
+      hipError_t e = hipMemcpyAsync(r->tparams.p, target.params, sizeof(double) * np,
+                                    hipMemcpyDeviceToDevice, c->stream);
+      if (e != hipSuccess) return bail(fail(VB_EDEVICE, "hipMemcpy failed: %s", hipGetErrorString(e)));
+      target.params = r->tparams.d();
+    }
+    r->spec = make_spec(fi, target, obj);
     if ((rc = r->grad.reserve(sizeof(double) * P)) != VB_OK) return bail(rc);
   }
   if ((rc = r->lam.reserve(sizeof(double) * P * n_problems)) != VB_OK) return bail(rc);
@@ -2226,8 +2155,8 @@ int vb_log_weights(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const 
   VB_TRY(check_ctx(c));
   FamInfo fi;
   VB_TRY(check_family(fam, &fi));
-  TargetHeads heads;
-  VB_TRY(check_target(tgt, fi.D, &heads));
+  vbk::Target target;
+  VB_TRY(check_target(tgt, fi.D, &target));
   if (!lam || !noise || !lw_out || m < 0) return fail(VB_EINVAL, "null argument");
   Path path;
   VB_TRY(choose_path({fi.kind, tgt->kind, fi.D}, &path));
@@ -2249,13 +2178,10 @@ int vb_log_weights(vb_ctx* c, const vb_family* fam, const vb_target* tgt, const 
   if (path == Path::ColumnPair || path == Path::Block) {
     VB_HIP(vbk::launch_log_weights(fi, tgt->kind, m, dl.d, nz, dlw.d, dxs.d, c->stream));
   } else {
-    const double* tp;
-    double tc;
-    const int slot = (!fr || block_target(tgt->kind)) ? kSlotGlm : kSlotTparamsLw;
-    VB_TRY(target_params(c, slot, tgt, &tp, &tc));
+    VB_TRY(stage_target(c, tgt, &target));
     vbk::FrWork* W;
     VB_TRY(fr_work(c, &W));
-    const vbk::Spec f = make_spec(fi, tgt, nullptr, tp, tc, heads);
+    const vbk::Spec f = make_spec(fi, target, nullptr);
     if (path == Path::LowRank)
       VB_TRY(vbk::lrg_log_weights(W, f, dl.d, m, nz, dlw.d, dxs.d, c->stream));
     else if (frg)

@@ -1450,7 +1450,7 @@ struct FrWork {
   } wsnap_h{};
   // N x D / N
   Buf Z, X, G, s, logp, zz, r, rk;
-  Buf glm;  // regression / multilevel target: chunk partials (glm_target_eval, mlm_target_eval)
+  Buf glm;  // regression / multilevel target: chunk partials (target_eval)
   Buf lrg;  // the low-rank Gaussian family's own workspace (fr_extra, vb_lrg.hip)
   // pinned host staging for host-callback targets
   double *hx = nullptr, *hlp = nullptr, *hg = nullptr;
@@ -1572,42 +1572,6 @@ int host_target_eval(FrWork* W, const HostTarget& t, int D, long long n, const d
   return 0;
 }
 
-int glm_target_eval(FrWork* W, const GlmHead& h, int D, long long n, const double* tparams,
-                    const double* x, double* logp, double* grad, hipStream_t st) {
-  if (!tparams) return vb_set_error(-1, "regression target without parameters");
-  FR_HIP(W->glm.reserve(sizeof(double) * glm_scratch_doubles(D, n, h, grad != nullptr)));
-  FR_HIP(launch_glm_rows(D, n, h, tparams, x, logp, grad, W->glm.d(), st));
-  return 0;
-}
-
-int mlm_target_eval(FrWork* W, const MlmHead& h, int D, long long n, const double* tparams,
-                    const double* x, double* logp, double* grad, hipStream_t st) {
-  if (!tparams) return vb_set_error(-1, "multilevel target without parameters");
-  FR_HIP(W->glm.reserve(sizeof(double) * mlm_scratch_doubles(D, n, h, grad != nullptr)));
-  FR_HIP(launch_mlm_rows(D, n, h, tparams, x, logp, grad, W->glm.d(), st));
-  return 0;
-}
-
-namespace {
-int eval_target(FrWork* W, const Spec& f, int D, long long n, const double* x, double* logp,
-                double* grad, hipStream_t st) {
-  const int tgt = f.tgt;
-  if (tgt == kTargetCallback) return host_target_eval(W, f.host, D, n, x, logp, grad, st);
-  if (tgt == kTargetPlugin) return plugin_target_eval(f.plugin, D, n, f.tparams, x, logp, grad, st);
-  if (tgt == kTargetRegression)
-    return glm_target_eval(W, f.glm, D, n, f.tparams, x, logp, grad, st);
-  if (tgt == kTargetHierarchical) {
-    if (!f.tparams) return vb_set_error(-1, "hierarchical target without parameters");
-    FR_HIP(launch_hier_rows(D, n, f.hier, f.tparams, x, logp, grad, st));
-    return 0;
-  }
-  if (tgt == kTargetMultilevel)
-    return mlm_target_eval(W, f.mlm, D, n, f.tparams, x, logp, grad, st);
-  FR_HIP(launch_target_logdensity(tgt, D, n, x, logp, grad, st));
-  return 0;
-}
-}  // namespace
-
 // The workspace's row buffers for n rows of dimension D (vb_frg.hip).  The t
 // family's prepared next step is dropped: its draws live in the same buffers.
 int fr_rows(FrWork* W, int D, long long n, FrRows* out) {
@@ -1623,14 +1587,6 @@ int fr_extra(FrWork* W, size_t doubles, double** out) {
   FR_HIP(W->lrg.reserve(sizeof(double) * std::max<size_t>(doubles, 1)));
   *out = W->lrg.d();
   return 0;
-}
-
-// log p [n] and (grad non-null) its gradient [n][D] of any target at x [n][D]
-int fr_eval_target(FrWork* W, const Spec& f, long long n, const double* x, double* logp,
-                   double* grad, hipStream_t st) {
-  if (f.tgt == kTargetCorrGauss)
-    return fr_target(W, f.tgt, f.fam.D, n, f.tparams, f.tconst, x, logp, grad, st);
-  return eval_target(W, f, f.fam.D, n, x, logp, grad, st);
 }
 
 // L, eigh(L L^T) -> (w ascending, Vt rows = eigenvectors), half log det from the
@@ -1977,23 +1933,46 @@ int fr_transform(FrWork* W, int D, long long n, const double* mu, const double* 
   return 0;
 }
 
-// log p and gradient of a target at x (n x D)
-int fr_target(FrWork* W, int tgt, int D, long long n, const double* tparams, double tconst,
-              const double* x, double* logp, double* G, hipStream_t st) {
-  if (tgt == kTargetCorrGauss) {
-    double* g = G;
-    if (!g) {
-      if (int rc = reserve_n(W, D, n)) return rc;
-      g = W->G.d();
+// log p and gradient of a target at x (n x D): the one switch over the target kind
+int target_eval(FrWork* W, const Target& t, long long n, const double* x, double* logp,
+                double* grad, hipStream_t st) {
+  if (n == 0) return 0;
+  const int D = t.D;
+  switch (t.kind) {
+    case kTargetCorrGauss: {   // G = -P* x (into the workspace without a gradient), then the rows
+      double* g = grad;
+      if (!g) {
+        if (int rc = reserve_n(W, D, n)) return rc;
+        g = W->G.d();
+      }
+      FR_HIP(gemm(mm((int)n, D, D, x, false, t.params, false, g, -1.0), st));
+      hipLaunchKernelGGL(fr_rows_kernel, dim3(blocks(n, 4)), dim3(256), 0, st, D, n, nullptr, x, g,
+                         t.tconst, 1, nullptr, logp);
+      FR_HIP(hipGetLastError());
+      return 0;
     }
-    FR_HIP(gemm(mm((int)n, D, D, x, false, tparams, false, g, -1.0), st));
-    hipLaunchKernelGGL(fr_rows_kernel, dim3(blocks(n, 4)), dim3(256), 0, st, D, n, nullptr, x, g,
-                       tconst, 1, nullptr, logp);
-    FR_HIP(hipGetLastError());
-    return 0;
+    case kTargetCallback:
+      return host_target_eval(W, t.host, D, n, x, logp, grad, st);
+    case kTargetPlugin:
+      return plugin_target_eval(t.plugin, D, n, t.params, x, logp, grad, st);
+    case kTargetRegression:
+      if (!t.params) return vb_set_error(-1, "regression target without parameters");
+      FR_HIP(W->glm.reserve(sizeof(double) * glm_scratch_doubles(D, n, t.glm, grad != nullptr)));
+      FR_HIP(launch_glm_rows(D, n, t.glm, t.params, x, logp, grad, W->glm.d(), st));
+      return 0;
+    case kTargetHierarchical:
+      if (!t.params) return vb_set_error(-1, "hierarchical target without parameters");
+      FR_HIP(launch_hier_rows(D, n, t.hier, t.params, x, logp, grad, st));
+      return 0;
+    case kTargetMultilevel:
+      if (!t.params) return vb_set_error(-1, "multilevel target without parameters");
+      FR_HIP(W->glm.reserve(sizeof(double) * mlm_scratch_doubles(D, n, t.mlm, grad != nullptr)));
+      FR_HIP(launch_mlm_rows(D, n, t.mlm, t.params, x, logp, grad, W->glm.d(), st));
+      return 0;
+    default:
+      FR_HIP(launch_target_logdensity(t.kind, D, n, x, logp, grad, st));
+      return 0;
   }
-  FR_HIP(launch_target_logdensity(tgt, D, n, x, logp, G, st));
-  return 0;
 }
 
 // One KLVI / CHIVI value + gradient (vb.py:236-266) at lam, gradient into grad[P]
@@ -2031,8 +2010,8 @@ int fr_value_grad(FrWork* W, const Spec& f, const double* lam, const Noise& nz, 
   const int nlp = 2 * ((D + 31) / 32);
   bool lp_parts = false;
   // target
-  if (f.tgt == kTargetCorrGauss) {
-    GemmOp tg = mm(N, D, D, W->X.d(), false, f.tparams, false, W->G.d(), -1.0);
+  if (f.tgt.kind == kTargetCorrGauss) {
+    GemmOp tg = mm(N, D, D, W->X.d(), false, f.tgt.params, false, W->G.d(), -1.0);
     if (fused) {   // logp = 0.5 x . G + const from per-row partials
       tg.rp_w = W->X.d();
       tg.rp_part = W->lp_part.d();
@@ -2041,10 +2020,10 @@ int fr_value_grad(FrWork* W, const Spec& f, const double* lam, const Noise& nz, 
     FR_HIP(gemm(tg, st));
     if (!fused)
       hipLaunchKernelGGL(fr_rows_kernel, dim3(blocks(N, 4)), dim3(256), 0, st, D, (long long)N,
-                         (f.chivi || f.pd) ? z : nullptr, W->X.d(), W->G.d(), f.tconst, 1,
+                         (f.chivi || f.pd) ? z : nullptr, W->X.d(), W->G.d(), f.tgt.tconst, 1,
                          W->zz.d(), W->logp.d());
   } else {
-    if (int rc = eval_target(W, f, D, N, W->X.d(), W->logp.d(), W->G.d(), st)) return rc;
+    if (int rc = target_eval(W, f.tgt, N, W->X.d(), W->logp.d(), W->G.d(), st)) return rc;
     if (!fused && (f.chivi || f.pd))
       hipLaunchKernelGGL(fr_rows_kernel, dim3(blocks(N, 4)), dim3(256), 0, st, D, (long long)N,
                          z, nullptr, nullptr, 0.0, 0, W->zz.d(), nullptr);
@@ -2054,13 +2033,13 @@ int fr_value_grad(FrWork* W, const Spec& f, const double* lam, const Noise& nz, 
   if (weights_fused() && N <= 512 && gemm_detail::glds_ok_shape(g)) {
     WeightsArgs wa{N, D, f.chivi, f.pd, f.alpha, f.fam.df, f.fam.t_const, W->logp.d(), W->zz.d(), s,
                    W->scal.d(), W->r.d(), W->rk.d(), value,
-                   lp_parts ? W->lp_part.d() : nullptr, lp_parts ? nlp : 0, f.tconst};
+                   lp_parts ? W->lp_part.d() : nullptr, lp_parts ? nlp : 0, f.tgt.tconst};
     FR_HIP(gemm_hook<WeightsHook>(g, wa, st));
   } else {
     hipLaunchKernelGGL(fr_weights_kernel, dim3(1), dim3(1024), 0, st, N, D, f.chivi, f.pd, f.alpha,
                        f.fam.df, f.fam.t_const, W->logp.d(), W->zz.d(), s, W->scal.d(), W->r.d(),
                        W->rk.d(), value, lp_parts ? W->lp_part.d() : nullptr, lp_parts ? nlp : 0,
-                       f.tconst);
+                       f.tgt.tconst);
     g.kscale = W->rk.d();
     FR_HIP(gemm(g, st));
   }
@@ -2157,12 +2136,12 @@ int fr_log_weights(FrWork* W, const Spec& f, const double* lam, long long m, con
   if (int rc = fr_draw(W, f.fam, m, nz, &s, &z, st)) return rc;
   double* x = xs ? xs : W->X.d();
   if (int rc = fr_transform(W, D, m, lam, s, z, x, st)) return rc;
-  if (f.tgt == kTargetCorrGauss) {
-    FR_HIP(gemm(mm((int)m, D, D, x, false, f.tparams, false, W->G.d(), -1.0), st));
+  if (f.tgt.kind == kTargetCorrGauss) {
+    FR_HIP(gemm(mm((int)m, D, D, x, false, f.tgt.params, false, W->G.d(), -1.0), st));
     hipLaunchKernelGGL(fr_rows_kernel, dim3(blocks(m, 4)), dim3(256), 0, st, D, m, z, x, W->G.d(),
-                       f.tconst, 1, W->zz.d(), W->logp.d());
+                       f.tgt.tconst, 1, W->zz.d(), W->logp.d());
   } else {
-    if (int rc = eval_target(W, f, D, m, x, W->logp.d(), nullptr, st)) return rc;
+    if (int rc = target_eval(W, f.tgt, m, x, W->logp.d(), nullptr, st)) return rc;
     hipLaunchKernelGGL(fr_rows_kernel, dim3(blocks(m, 4)), dim3(256), 0, st, D, m, z, nullptr,
                        nullptr, 0.0, 0, W->zz.d(), nullptr);
   }
@@ -2416,22 +2395,21 @@ int mf_wide_value_grad(FrWork* W, const Spec& f, const double* lam, const Noise&
   const int D = f.fam.D, N = f.N;
   if (int rc = reserve_d(W, 1, st)) return rc;
   if (int rc = reserve_n(W, D, N)) return rc;
-  if (f.tgt == kTargetCorrGauss)
+  if (f.tgt.kind == kTargetCorrGauss)
     return vb_set_error(-4, "corr_gauss is implemented for the full-rank family only");
   // per-row log p / log q: one value per row, or chunk partials of the fused kernel (in Z,
   // unused on this path: nparts * N * 2 <= N * D for D >= 512)
   int nparts = 1;
   double *lp = W->logp.d(), *lq = W->zz.d();
-  if (mfw_rows_fusable(f.tgt, D, N)) {
+  if (mfw_rows_fusable(f.tgt.kind, D, N)) {
     nparts = mfw_rows_parts(D);
     lp = W->Z.d();
     lq = lp + (size_t)nparts * N;
-    FR_HIP(launch_mfw_rows(f.fam, f.tgt, N, lam, f.chivi || f.pd, nz, W->X.d(), W->G.d(), lp, lq,
-                           st));
+    FR_HIP(launch_mfw_rows(f.fam, f.tgt.kind, N, lam, f.chivi || f.pd, nz, W->X.d(), W->G.d(), lp,
+                           lq, st));
   } else {
     FR_HIP(launch_sample(f.fam, N, lam, nz, W->X.d(), st));
-    if (int rc = eval_target(W, f, D, N, W->X.d(), W->logp.d(), W->G.d(), st))
-      return rc;
+    if (int rc = target_eval(W, f.tgt, N, W->X.d(), W->logp.d(), W->G.d(), st)) return rc;
     if (f.chivi || f.pd)
       FR_HIP(launch_family_logdensity(f.fam, N, lam, W->X.d(), W->zz.d(), st));
   }
@@ -2497,7 +2475,7 @@ int mf_wide_log_weights(FrWork* W, const Spec& f, const double* lam, long long m
   } else {
     FR_HIP(launch_sample(f.fam, m, lam, nz, x, st));
   }
-  if (int rc = eval_target(W, f, D, m, x, W->logp.d(), nullptr, st)) return rc;
+  if (int rc = target_eval(W, f.tgt, m, x, W->logp.d(), nullptr, st)) return rc;
   FR_HIP(launch_family_logdensity(f.fam, m, lam, x, W->zz.d(), st));
   hipLaunchKernelGGL(sub_kernel, dim3(blocks(m)), dim3(256), 0, st, m, W->logp.d(), W->zz.d(), lw);
   FR_HIP(hipGetLastError());

@@ -13,7 +13,7 @@
 //                       sum M_ii
 //   2 frg_x_kernel      X = mu + Z L^T on v_mfma_f64_16x16x4_f64, L read from the
 //                       packed parameters; k tiles above the diagonal tile are skipped
-//     target            log p, G = d log p / dx (fr_eval_target)
+//     target            log p, G = d log p / dx (target_eval)
 //   3 frg_grad_kernel   weights r_n in every block's prologue (fixed order, the
 //                       same bits in every block), then the lower-triangle tiles of
 //                       G_L = G^T diag(r) Z (depth N) and the mean gradient
@@ -370,7 +370,7 @@ int frg_value_grad(FrWork* W, const Spec& f, const double* lam, const Noise& nz,
   if (int rc = fr_rows(W, D, N, &b)) return rc;
   const double* z;
   if (int rc = draw_transform(b, D, N, lam, nz, true, b.X, &z, st)) return rc;
-  if (int rc = fr_eval_target(W, f, N, b.X, b.logp, b.G, st)) return rc;
+  if (int rc = target_eval(W, f.tgt, N, b.X, b.logp, b.G, st)) return rc;
   FrgGradArgs a{};
   a.D = D;
   a.N = N;
@@ -420,7 +420,7 @@ int frg_log_weights(FrWork* W, const Spec& f, const double* lam, long long m, co
   double* x = xs ? xs : b.X;
   const double* z;
   if (int rc = draw_transform(b, D, m, lam, nz, true, x, &z, st)) return rc;
-  if (int rc = fr_eval_target(W, f, m, x, b.logp, nullptr, st)) return rc;
+  if (int rc = target_eval(W, f.tgt, m, x, b.logp, nullptr, st)) return rc;
   hipLaunchKernelGGL(frg_lw_kernel, dim3((unsigned)cdiv(m, 256)), dim3(256), 0, st, D, m, b.logp,
                      b.zz, b.scal, lw);
   FRG_HIP(hipGetLastError());

@@ -334,20 +334,38 @@ struct FrWork;  // per-context workspace + rocBLAS handle
 FrWork* fr_work_create();
 void fr_work_destroy(FrWork* w);
 
+// A checked target (check_target in vb_capi.hip), with everything a launch needs.  A
+// kind is wired in three places: its header parse in check_target fills the member of
+// the union that belongs to it, target_eval (vb_fr.hip) has its case, and choose_path
+// (vb_capi.hip) says which paths take it.  stage_target puts `params` on the device.
+struct Target {
+  int kind = 0, D = 0;
+  const double* params = nullptr;  // device; corr_gauss: P* [D][D] and the log normaliser;
+                                   // regression / hierarchical / multilevel / plugin: the block
+  long long n_params = 0;          // doubles at params
+  double tconst = 0.0;             // corr_gauss log normaliser
+  union {                          // only the kind's own member is meaningful
+    GlmHead glm;                   // kTargetRegression
+    HierHead hier;                 // kTargetHierarchical
+    MlmHead mlm;                   // kTargetMultilevel
+    PluginTarget plugin;           // kTargetPlugin
+    HostTarget host;               // kTargetCallback
+  };
+  Target() : glm{} {}
+};
+// log p [n] and (grad non-null) d log p / dx [n][D] of the rows of device x [n][D]: the one
+// switch over the target kind.  The regression and multilevel chunk partials are reserved
+// in the workspace; a callback synchronises; n == 0 evaluates nothing.
+int target_eval(FrWork* W, const Target& t, long long n, const double* x, double* logp,
+                double* grad, hipStream_t st);
+
 // What the full-rank and the materialised mean-field paths evaluate: family, target
 // and objective (N = 0 and no objective flags for log weights).
 struct Spec {
   Family fam;
-  int N, tgt, chivi, pd;
+  int N, chivi, pd;
   double alpha;
-  const double* tparams;  // device; corr_gauss: P*[D][D]; regression / hierarchical /
-                          // multilevel: the block
-  double tconst;          // corr_gauss log normaliser
-  HostTarget host;        // tgt == kTargetCallback
-  GlmHead glm;            // tgt == kTargetRegression
-  HierHead hier;          // tgt == kTargetHierarchical
-  MlmHead mlm;            // tgt == kTargetMultilevel
-  PluginTarget plugin;    // tgt == kTargetPlugin (tparams: its data block)
+  Target tgt;
 };
 
 // All return 0 or a VB_E* code (message via vb_set_error).
@@ -362,14 +380,6 @@ int fr_draw(FrWork* W, const Family& f, long long n, const Noise& nz, const doub
             const double** z_out, hipStream_t st);
 int fr_transform(FrWork* W, int D, long long n, const double* mu, const double* s,
                  const double* z, double* x, hipStream_t st);
-int fr_target(FrWork* W, int tgt, int D, long long n, const double* tparams, double tconst,
-              const double* x, double* logp, double* G, hipStream_t st);
-// regression target at device x [n][D] (grad nullable); chunk partials in the workspace
-int glm_target_eval(FrWork* W, const GlmHead& h, int D, long long n, const double* tparams,
-                    const double* x, double* logp, double* grad, hipStream_t st);
-// multilevel target at device x [n][D] (grad nullable); chunk partials in the workspace
-int mlm_target_eval(FrWork* W, const MlmHead& h, int D, long long n, const double* tparams,
-                    const double* x, double* logp, double* grad, hipStream_t st);
 struct MfUpdate;
 // The next step of a fused run: its draws (rng step `step`) and L are prepared by
 // this step's last kernel when `prep`.
@@ -439,9 +449,6 @@ struct FrRows {
   double *Z, *X, *G, *logp, *zz, *scal;
 };
 int fr_rows(FrWork* W, int D, long long n, FrRows* out);
-// eval_target for every target kind (corr_gauss through fr_target)
-int fr_eval_target(FrWork* W, const Spec& f, long long n, const double* x, double* logp,
-                   double* grad, hipStream_t st);
 // nz.eps (host draws) = z [n][D] on the device, N(0,1)
 int frg_sample(FrWork* W, const Family& f, const double* lam, long long n, const Noise& nz,
                double* x, hipStream_t st);

@@ -21,7 +21,7 @@
 //   4 lrg_noise_kernel     eps rows from Philox at width D + R (host draws are read in place)
 //   5 lrg_x_kernel         X = mu + d z + U B^T on v_mfma_f64_16x16x4_f64 (depth R,
 //                          zero-padded in registers)
-//     target               log p, G = d log p / dx (fr_eval_target)
+//     target               log p, G = d log p / dx (target_eval)
 //   6 lrg_quad_kernel      per sample: t_n, a_n = rho_n / d, q_n = |rho_n|^2 + |t_n|^2
 //                          (KLVI_PD, CHIVI and log weights; KLVI needs no log q)
 //   7 lrg_grad_kernel      (KLVI: the entropy form; KLVI_PD and CHIVI: sum_n r_n grad lw_n,
@@ -549,7 +549,7 @@ int lrg_value_grad(FrWork* W, const Spec& f, const double* lam, const Noise& nz,
   if (int rc = capacitance(w, D, R, lam, true, st)) return rc;
   const double* eps;
   if (int rc = draw_transform(w, D, R, N, lam, nz, w.b.X, &eps, st)) return rc;
-  if (int rc = fr_eval_target(W, f, N, w.b.X, w.b.logp, w.b.G, st)) return rc;
+  if (int rc = target_eval(W, f.tgt, N, w.b.X, w.b.logp, w.b.G, st)) return rc;
   const int mode = f.chivi ? 1 : f.pd ? 2 : 0;
   if (mode != 0)
     if (int rc = quad(w, D, R, N, lam, eps, nullptr, nullptr, st)) return rc;
@@ -606,7 +606,7 @@ int lrg_log_weights(FrWork* W, const Spec& f, const double* lam, long long m, co
   double* x = xs ? xs : w.b.X;
   const double* eps;
   if (int rc = draw_transform(w, D, R, m, lam, nz, x, &eps, st)) return rc;
-  if (int rc = fr_eval_target(W, f, m, x, w.b.logp, nullptr, st)) return rc;
+  if (int rc = target_eval(W, f.tgt, m, x, w.b.logp, nullptr, st)) return rc;
   if (int rc = quad(w, D, R, m, lam, eps, nullptr, nullptr, st)) return rc;
   hipLaunchKernelGGL(lrg_lw_kernel, dim3((unsigned)cdiv(m, 256)), dim3(256), 0, st, D, m, w.b.logp,
                      w.qq, w.b.scal, lw);
