@@ -27,6 +27,12 @@ def _lib():
         lib.vbo_fr_scale.argtypes = [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
                                      ctypes.c_int64, ctypes.c_double,
                                      ctypes.POINTER(ctypes.c_double)]
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        lib.vbo_draw_ints.argtypes = [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                      ctypes.c_int64, ctypes.c_int64, i64p, i64p, i64p, i64p]
+        lib.vbo_scan_tails.argtypes = [ctypes.c_uint64] + [ctypes.c_uint32] * 5 + [
+            ctypes.c_int64, ctypes.c_int64, i64p]
+        lib.vbo_scan_tails.restype = ctypes.c_int64
         _LIB = lib
     return _LIB
 
@@ -56,3 +62,25 @@ def fr_noise(seed, stream, step, n, dim, df):
     _lib().vbo_fr_scale(seed, stream & 0xFFFFFF, step & 0xFFFFFFFF, n, float(df),
                         s.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
     return s, noise(seed, stream, step, n, dim, 'gauss')
+
+
+def draw_ints(seed, stream, step, n, dim):
+    """The integers behind one step's draws (vbrng.c vbo_draw_ints): Bailey a [n, dim]
+    (40 bits) and b [n, dim] (24 bits), and the Gaussian pairs' 52-bit mantissas m1, m2
+    [n, (dim + 1) // 2]."""
+    npairs = (dim + 1) // 2
+    a, b = np.zeros((n, dim), dtype=np.int64), np.zeros((n, dim), dtype=np.int64)
+    m1, m2 = np.zeros((n, npairs), dtype=np.int64), np.zeros((n, npairs), dtype=np.int64)
+    p = ctypes.POINTER(ctypes.c_int64)
+    _lib().vbo_draw_ints(seed, stream & 0xFFFFFF, step & 0xFFFFFFFF, n, dim,
+                         *(v.ctypes.data_as(p) for v in (a, b, m1, m2)))
+    return a, b, m1, m2
+
+
+def scan_tails(seed, stream0, nstreams, nsteps, nrows, npairs, a_lo=1 << 12, cap=1 << 16):
+    """Bailey variates in the tails over a block of streams (vbrng.c vbo_scan_tails):
+    an int64 array of rows (stream, step, row, pair, c, a, b)."""
+    out = np.zeros((cap, 7), dtype=np.int64)
+    n = _lib().vbo_scan_tails(seed, stream0, nstreams, nsteps, nrows, npairs, a_lo, cap,
+                              out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)))
+    return out[:min(n, cap)]

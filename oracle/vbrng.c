@@ -148,6 +148,59 @@ void vbo_fill(uint64_t seed, uint32_t stream, uint32_t step, int64_t nrows, int6
   }
 }
 
+/* The integers the draws of one step are formed from, for references that start
+ * from them (tests/logw_mp.py).  Bailey variate d of row r (bailey_pair): a[r D + d]
+ * (40 bits, U1 = (a + 1/2) 2^-40) and b[r D + d] (24 bits, U2 = b 2^-24).  Gaussian
+ * pair j of row r (gauss2): m1[r npairs + j], m2[r npairs + j], the two 52-bit
+ * mantissas (u1 = (2 m1 + 1) 2^-53, u2 = m2 2^-52). */
+void vbo_draw_ints(uint64_t seed, uint32_t stream, uint32_t step, int64_t nrows, int64_t D,
+                   int64_t* a, int64_t* b, int64_t* m1, int64_t* m2) {
+  int64_t npairs = (D + 1) / 2;
+  for (int64_t r = 0; r < nrows; ++r)
+    for (int64_t j = 0; j < npairs; ++j) {
+      blk w = draw(seed, stream, (uint32_t)j, (uint32_t)r, step, VBO_BAILEY_PURPOSE);
+      for (int c = 0; c < 2 && 2 * j + c < D; ++c) {
+        uint32_t lo = w.v[c], hi = w.v[2 + c];
+        a[r * D + 2 * j + c] = (int64_t)((((uint64_t)(hi & 0xffu)) << 32) | lo);
+        b[r * D + 2 * j + c] = (int64_t)(hi >> 8);
+      }
+      blk g = draw(seed, stream, (uint32_t)j, (uint32_t)r, step, 0u);
+      m1[r * npairs + j] = (int64_t)(((((uint64_t)g.v[1]) << 32) | g.v[0]) >> 12);
+      m2[r * npairs + j] = (int64_t)(((((uint64_t)g.v[3]) << 32) | g.v[2]) >> 12);
+    }
+}
+
+/* Scan streams [stream0, stream0 + nstreams) x steps [0, nsteps) x rows [0, nrows) x
+ * pairs [0, npairs) for Bailey variates in the tails: a < a_lo, a > 2^40 - a_lo, or b
+ * within 1 (mod 2^24) of a multiple of 2^22 (cos(2 pi U2) at and beside its zeros and
+ * extrema).  Each hit: 7 entries (stream, step, row, pair, c, a, b) of out; at most cap
+ * are written, the count of all is returned (scripts/find_logw_tail_streams.py). */
+int64_t vbo_scan_tails(uint64_t seed, uint32_t stream0, uint32_t nstreams, uint32_t nsteps,
+                       uint32_t nrows, uint32_t npairs, int64_t a_lo, int64_t cap, int64_t* out) {
+  int64_t n = 0;
+  const int64_t a_hi = ((int64_t)1 << 40) - a_lo;
+  for (uint32_t s = stream0; s < stream0 + nstreams; ++s)
+    for (uint32_t st = 0; st < nsteps; ++st)
+      for (uint32_t r = 0; r < nrows; ++r)
+        for (uint32_t j = 0; j < npairs; ++j) {
+          blk w = draw(seed, s, j, r, st, VBO_BAILEY_PURPOSE);
+          for (int c = 0; c < 2; ++c) {
+            uint32_t lo = w.v[c], hi = w.v[2 + c];
+            int64_t a = (int64_t)((((uint64_t)(hi & 0xffu)) << 32) | lo);
+            uint32_t b = hi >> 8;
+            uint32_t off = (b + 1u) & 0x3fffffu;          /* b = k 2^22 - 1, k 2^22, k 2^22 + 1 */
+            if (a < a_lo || a > a_hi || off <= 2u) {
+              if (n < cap) {
+                int64_t* o = out + 7 * n;
+                o[0] = s; o[1] = st; o[2] = r; o[3] = j; o[4] = c; o[5] = a; o[6] = b;
+              }
+              ++n;
+            }
+          }
+        }
+  return n;
+}
+
 /* full-rank t scale draws s[n] = sqrt(chisquare(df)/df) = sqrt(2 Gamma(df/2)/df)
  * from the reserved column pair 0xFFFFFFFF (vb_fr.hip fr_noise_kernel) */
 void vbo_fr_scale(uint64_t seed, uint32_t stream, uint32_t step, int64_t nrows, double df,
