@@ -192,7 +192,8 @@ enum vb_target_kind {
  *   params[4] prior_scale s (> 0)
  *   params[5] G (number of groups, >= 1, integral)
  *   params[6] s_tau (> 0)
- *   params[7] form: 0 non-centred, 1 centred
+ *   params[7] form + 2 learn: 0 non-centred, 1 centred; 2 non-centred and 3 centred with
+ *             learn = 1 (below)
  *   params[8 ..]                X, row-major [M][p]
  *   params[8 + M*p ..]          y [M]   (bernoulli_logit: 0 or 1)
  *   params[8 + M*p + M ..]      off [G + 1]: group g holds the observations
@@ -203,6 +204,21 @@ enum vb_target_kind {
  *   params[8 + M*p + M + G + 1 ..]    eta0 [M], in the observations' sorted order
  *   params[8 + M*p + 2 M + G + 1]     c_data
  *   n_params = 8 + M*p + M + (G + 1) + M + 1
+ * learn = 1 (params[7] = 2 or 3; likelihoods 0, 1 and 4 only): the scale or dispersion is a
+ * coordinate, the last one: x = [beta (p), u, then G more, lambda], dim = p + 2 + G, every
+ * other offset of x as above; lambda = log sigma (likelihoods 0, 1) or log phi (4), with
+ * e^lambda ~ half-Cauchy(0, s_aux) written in lambda with its Jacobian, as learn = 1 of
+ * VB_TARGET_REGRESSION: log p(lambda) = log(2 / (pi s_aux)) - softplus(w) + lambda,
+ * w = 2 (lambda - log s_aux).  X is [M][p] with p = dim - 2 - G.  The vacated constant
+ * (params[3] for likelihoods 0 and 1, params[2] for likelihood 4) is packed as 0 and not
+ * read.  The block is the fixed block of the same likelihood with a tail behind it:
+ *   likelihoods 0, 1:  .. off [G + 1] | s_aux
+ *                      n_params = 8 + M*p + M + G + 1 + 1
+ *   likelihood 4:      .. off [G + 1] | eta0 [M] | c_data | s_aux | J | T [J]
+ *                      n_params = 8 + M*p + 2 M + G + 1 + 1 + 1 + 1 + J
+ * s_aux > 0; J an integer in [0, 65536]; T[j] = #{m : y_m > j} and c_data = sum_m
+ * -lgamma(y_m + 1), as in the learned regression block.  VB_ABI_VERSION is unchanged: every
+ * block with params[7] = 0 or 1 reads as before.
  * Staged and copied as the regression block is. */
 
 /* VB_TARGET_PLUGIN -- device model plugins.  A model is a gfx950 code object (a raw

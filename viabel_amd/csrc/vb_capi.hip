@@ -741,28 +741,64 @@ int multilevel_head(const vb_target* t, vbk::MlmHead* o) {
   VB_TRY(b.choice(0, "likelihood", 4));
   VB_TRY(b.count(1, "M", 9.0e15));
   const int lik = (int)h[0];
+  VB_TRY(b.choice(7, "form + 2 learn", 3));
+  // learn: the last coordinate is log sigma (0, 1) or log phi (4)
+  const bool learn = h[7] >= 2.0;
+  if (learn && (lik == 2 || lik == 3))
+    return fail(VB_EINVAL,
+                "multilevel target: params[7] (form + 2 learn) = %g sets learn = 1, which is valid for "
+                "the likelihoods 0, 1 and 4 (gaussian, student_t, neg_binomial_2_log), not for %d",
+                h[7], lik);
   if (lik == 1) VB_TRY(b.positive(2, "nu"));
-  if (lik == 4) VB_TRY(b.positive(2, "phi"));
-  if (lik < 2) VB_TRY(b.positive(3, "sigma"));
+  if (lik == 4 && !learn) VB_TRY(b.positive(2, "phi"));
+  if (lik < 2 && !learn) VB_TRY(b.positive(3, "sigma"));
   VB_TRY(b.positive(4, "prior_scale"));
   VB_TRY(b.count(5, "G", 2.0e9));
   VB_TRY(b.positive(6, "tau_scale"));
-  VB_TRY(b.choice(7, "form", 1));
-  const double p = (double)t->dim - 1.0 - h[5];
+  o->G = (long long)h[5];
+  o->learn = learn ? 1 : 0;
+  const double p = (double)vbk::mlm_coefs(t->dim, *o);
   if (!(p >= 1.0))
-    return fail(VB_EINVAL, "multilevel target: dim %lld does not leave p >= 1 beside 1 + G = %.0f",
-                (long long)t->dim, 1.0 + h[5]);
+    return fail(VB_EINVAL, "multilevel target: dim %lld does not leave p >= 1 beside 1 + G%s = %.0f",
+                (long long)t->dim, learn ? " + 1 (learn)" : "", 1.0 + h[5] + (learn ? 1.0 : 0.0));
   const bool count = lik >= 3;   // eta0 [M] and c_data follow the group offsets
   const double tail = count ? h[1] + 1.0 : 0.0;
-  const double want = (double)vbk::kMlmHeader + h[1] * p + h[1] + h[5] + 1.0 + tail;
-  if ((double)t->n_params != want)
+  // what a fixed block has; a learned block goes on: s_aux, and for likelihood 4 J, T [J]
+  const double base = (double)vbk::kMlmHeader + h[1] * p + h[1] + h[5] + 1.0 + tail;
+  double s_aux = 0.0, J = 0.0;
+  if (learn) {
+    const double least = base + (lik == 4 ? 2.0 : 1.0);
+    if ((double)t->n_params < least)
+      return fail(VB_EINVAL,
+                  "multilevel target: n_params %lld is shorter than 8 + M*p + M + G + 1%s = %.0f (M %.0f, "
+                  "p %.0f, G %.0f)", (long long)t->n_params, lik == 4 ? " + M + 1 + 1 + 1" : " + 1",
+                  least, h[1], p, h[5]);
+    VB_TRY(b.read((size_t)base, &s_aux));
+    if (!(s_aux > 0.0 && std::isfinite(s_aux)))
+      return fail(VB_EINVAL, "multilevel target: s_aux (after %s) must be positive, got %g",
+                  lik == 4 ? "c_data" : "the group offsets", s_aux);
+    if (lik == 4) {
+      VB_TRY(b.read((size_t)base + 1, &J));
+      if (!(J >= 0.0 && J <= 65536.0 && J == std::floor(J)))
+        return fail(VB_EINVAL, "multilevel target: J (the table's length, after s_aux) must be an "
+                    "integer in [0, 65536], got %g", J);
+    }
+  }
+  const double want = base + (learn ? 1.0 + (lik == 4 ? 1.0 + J : 0.0) : 0.0);
+  if ((double)t->n_params != want) {
+    if (learn)
+      return fail(VB_EINVAL,
+                  "multilevel target: n_params %lld does not match 8 + M*p + M + G + 1%s = %.0f (M %.0f, "
+                  "p = dim - 2 - G = %.0f, G %.0f)", (long long)t->n_params,
+                  lik == 4 ? " + M + 1 + 1 + 1 + J" : " + 1", want, h[1], p, h[5]);
     return fail(VB_EINVAL,
                 "multilevel target: n_params %lld does not match 8 + M*p + M + G + 1%s = %.0f (M %.0f, "
                 "p %.0f, G %.0f)", (long long)t->n_params, count ? " + M + 1" : "", want, h[1], p, h[5]);
+  }
   // the group offsets: exact integers, 0 first, M last, non-decreasing
   const size_t ng = (size_t)h[5] + 1;
   std::vector<double> off(ng);
-  VB_TRY(b.read((size_t)(want - tail - (double)ng), off.data(), ng));
+  VB_TRY(b.read((size_t)(base - tail - (double)ng), off.data(), ng));
   if (off[0] != 0.0)
     return fail(VB_EINVAL, "multilevel target: the first group offset must be 0, got %g", off[0]);
   if (off[ng - 1] != h[1])
@@ -774,16 +810,17 @@ int multilevel_head(const vb_target* t, vbk::MlmHead* o) {
                   "multilevel target: group offsets must be non-decreasing integers, got %g after %g "
                   "at group %lld", off[g], off[g - 1], (long long)g);
   o->lik = lik;
-  o->centered = (int)h[7];
+  o->centered = (int)h[7] & 1;
   o->M = (long long)h[1];
-  o->G = (long long)h[5];
   o->nu = h[2];
-  o->sigma = h[3];
+  o->sigma = learn ? 0.0 : h[3];
   o->prior = h[4];
   o->tau_scale = h[6];
-  o->phi = lik == 4 ? h[2] : 0.0;
+  o->phi = lik == 4 && !learn ? h[2] : 0.0;
   o->c_data = 0.0;
-  if (count) VB_TRY(b.c_data((size_t)t->n_params - 1, &o->c_data));
+  o->s_aux = s_aux;
+  o->J = (long long)J;
+  if (count) VB_TRY(b.c_data((size_t)base - 1, &o->c_data));
   return VB_OK;
 }
 

@@ -41,6 +41,8 @@
 // pla [nchunk][n] beside plp.  The gaussian needs none: sum_m (-1 + r^2 / sigma^2) =
 // -M - 2 sum_m l_m.  The negative binomial's table sums A(phi) = sum_j T_j log1p(j / phi)
 // and dA/dlambda = -sum_j T_j j / (phi + j) are formed once per call by glm_disp_kernel.
+// The learned links, the prior of lambda and the table sums are defined in vb_links.hpp,
+// which vb_mlm.hip's learned instances share.
 #include <algorithm>
 #include <cmath>
 
@@ -84,56 +86,8 @@ struct GlmK {
   double* pla;             // [nchunk][n]  (nchunk > 1, grad; LIK 6, 7)
 };
 
-// the learned instances: LIK = 5, 6, 7 are likelihoods 0, 1, 4 with lambda a coordinate
-constexpr bool glm_learned(int lik) { return lik >= 5; }
-constexpr bool glm_offset(int lik) { return link_has_offset(lik) || lik == 7; }
-
 __device__ __forceinline__ double glm_final_logp(const GlmK& k, double sum_l, double ss) {
   return k.c_all + (sum_l - 0.5 * k.inv_s2 * ss);
-}
-
-// learned mode: a row's link constants from its lambda.  gaussian, student_t: ca =
-// 1 / sigma = exp(-lambda) (the residual is scaled before it is squared, so a residual of
-// exactly 0 stays 0 where sigma^2 leaves the range); neg_binomial: ca = phi, cb = lambda
-template <int LIK>
-__device__ __forceinline__ void glm_row_consts(double lam, double& ca, double& cb) {
-  if constexpr (LIK == 7) {
-    ca = exp(lam);
-    cb = lam;
-  } else {
-    ca = exp(-lam);
-    cb = 0.0;
-  }
-}
-
-// l(y, eta) without its constant and without -lambda, dl / d eta, and the observation's
-// share of dl / d lambda without its -1 (LIK 5: not formed, -M - 2 sum l serves)
-template <int LIK>
-__device__ __forceinline__ void glm_link_aux(const GlmK& k, double ca, double cb, double eta,
-                                             double y, double& l, double& dl, double& dlam) {
-  if constexpr (LIK == 5) {          // q = r / sigma
-    const double q = (y - eta) * ca;
-    l = -0.5 * (q * q);
-    dl = q * ca;
-    dlam = 0.0;
-  } else if constexpr (LIK == 6) {   // t = (nu + 1) q / (nu + q^2): dl = t / sigma, dlam = t q
-    const double q = (y - eta) * ca;
-    const double q2 = q * q;
-    l = -k.lk.k1 * log1p(q2 * k.inv_nu);
-    const double t = k.lk.k2 * q / (k.nu + q2);
-    dl = t * ca;
-    dlam = t * q;
-  } else {                           // phi = ca, zeta = eta - lambda
-    const double z = eta - cb;
-    const double e = exp(-fabs(z));
-    const double yp = y + ca;
-    const double sp = fmax(z, 0.0) + log1p(e);
-    l = y * eta - yp * sp;
-    const double inv = 1.0 / (1.0 + e);
-    const double lg = yp * (z >= 0.0 ? inv : e * inv);
-    dl = y - lg;
-    dlam = lg - ca * sp;             // (y - dl) - phi softplus(zeta)
-  }
 }
 
 // learned mode: log p and d log p / d lambda of one row from its reduced sums: the prior
@@ -144,11 +98,8 @@ template <int LIK>
 __device__ __forceinline__ void glm_aux_final(const GlmK& k, long long row, double lam,
                                               double sum_l, double sum_la, double ss, double& lp,
                                               double& gl) {
-  const double w = 2.0 * (lam - k.ls_aux);
-  const double e = exp(-fabs(w));
-  const double sp = fmax(w, 0.0) + log1p(e);
-  const double inv = 1.0 / (1.0 + e);
-  const double lg = w >= 0.0 ? inv : e * inv;
+  double sp, lg;
+  aux_lambda_prior(lam, k.ls_aux, sp, lg);
   const double v = k.c_all + (sum_l - 0.5 * k.inv_s2 * ss);
   const double gp = 1.0 - 2.0 * lg;
   if constexpr (LIK == 7) {
@@ -167,8 +118,8 @@ __device__ __forceinline__ void glm_aux_final(const GlmK& k, long long row, doub
 template <int LIK, bool GRAD, int DP>
 __global__ __launch_bounds__(256) void glm_rows_small_kernel(GlmK k) {
   __shared__ double Xs[kGlmTile * DP];
-  constexpr bool OFFS = glm_offset(LIK);        // eta0 rides behind y in the tile
-  constexpr bool LRN = glm_learned(LIK);
+  constexpr bool OFFS = link_offset(LIK);       // eta0 rides behind y in the tile
+  constexpr bool LRN = link_learned(LIK);
   __shared__ double ys[OFFS ? 2 * kGlmTile : kGlmTile];
   const int t = threadIdx.x, nt = blockDim.x, D = k.D;
   const int Dx = LRN ? k.Dx : D;                // row stride of x and grad
@@ -267,8 +218,8 @@ __device__ __forceinline__ void glm_stage(double* dst, const double* src, long l
 
 template <int LIK, bool GRAD, int NCT>
 __global__ __launch_bounds__(256) void glm_rows_mfma_kernel(GlmK k) {
-  constexpr bool OFFS = glm_offset(LIK);
-  constexpr bool LRN = glm_learned(LIK);
+  constexpr bool OFFS = link_offset(LIK);
+  constexpr bool LRN = link_learned(LIK);
   constexpr bool LACC = LRN && GRAD && LIK != 5;   // a second per-row accumulator
   // learned mode: the 16 rows' link constants (ca, cb) behind the waves' tiles
   __shared__ double smem[4 * kGlmWave + (LRN ? 32 : 0)];
@@ -490,35 +441,10 @@ __global__ __launch_bounds__(256) void glm_combine_aux_kernel(GlmK k, int with_g
   }
 }
 
-// learned dispersion: A(phi) = sum_{j=1}^{J-1} T_j log1p(j / phi) and dA / dlambda =
-// -sum_j T_j j / (phi + j) of one sample row per block, phi = exp(lambda) as the row
-// kernels form it.  Every term has one sign.  Threads stride over j; the partial sums
-// meet by the wave reduction and then in wave order: the same bits every call.
+// learned dispersion: the table sums of the n rows (disp_row_sums of vb_links.hpp), one
+// sample row per block
 __global__ __launch_bounds__(256) void glm_disp_kernel(GlmK k) {
-  __shared__ double red[8];
-  const long long row = blockIdx.x;
-  const int t = threadIdx.x, w = t >> 6, lane = t & 63;
-  const double phi = exp(k.x[row * k.Dx + k.D]);
-  double a = 0.0, da = 0.0;
-  for (long long j = 1 + t; j < k.J; j += 256) {
-    const double tj = k.T[j], fj = (double)j;
-    a = fma(tj, log1p(fj / phi), a);
-    da = fma(tj, fj / (phi + fj), da);
-  }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    a += __shfl_xor(a, off, 64);
-    da += __shfl_xor(da, off, 64);
-  }
-  if (lane == 0) {
-    red[w] = a;
-    red[4 + w] = da;
-  }
-  __syncthreads();
-  if (t == 0) {
-    k.tab[row] = ((red[0] + red[1]) + red[2]) + red[3];
-    k.tab[k.n + row] = -(((red[4] + red[5]) + red[6]) + red[7]);
-  }
+  disp_row_sums(k.x, k.Dx, k.D, k.T, k.J, k.tab, k.n);
 }
 
 int glm_cu_count() {
@@ -632,25 +558,14 @@ static hipError_t launch_glm_rows_aux(int D, long long n, const GlmHead& h, cons
   k.M = h.M;
   k.Mf = (double)h.M;
   k.chunk_obs = p.chunk_obs;
-  // The fixed link's constants at sigma = 1: c_obs without -log sigma (-M lambda is the
-  // row's), and the student_t's k1, k2.  Not its k0, k3, which hold sigma; and nothing of
-  // the negative binomial's, whose phi and log phi are the row's.
-  double c_obs = 0.0;
-  if (h.lik != 4) {
-    LinkK fixed;
-    c_obs = link_consts(h.lik, h.nu, 1.0, 0.0, &fixed);
-    k.lk.k1 = fixed.k1;
-    k.lk.k2 = fixed.k2;
-  }
-  if (h.lik == 1) {
-    k.nu = h.nu;
-    k.inv_nu = 1.0 / h.nu;
-  }
+  const AuxConsts a = aux_consts(h.lik, h.nu, h.s_aux);   // vb_links.hpp
+  k.lk.k1 = a.k1;
+  k.lk.k2 = a.k2;
+  k.nu = a.nu;
+  k.inv_nu = a.inv_nu;
   k.inv_s2 = 1.0 / (h.prior * h.prior);
-  k.ls_aux = std::log(h.s_aux);
-  // log(2 / (pi s_aux)): the half-Cauchy's constant
-  k.c_all = -(double)pc * (0.5 * kLog2Pi + std::log(h.prior)) + (double)h.M * c_obs +
-            (-0.45158270528945486472619522989488 - k.ls_aux);
+  k.ls_aux = a.ls_aux;
+  k.c_all = -(double)pc * (0.5 * kLog2Pi + std::log(h.prior)) + (double)h.M * a.c_obs + a.c_aux;
   if (h.lik == 4) k.c_all += h.c_data;
   k.X = params + kGlmHeader;
   k.y = k.X + (size_t)h.M * pc;

@@ -284,12 +284,20 @@ struct MlmHead {
   int lik;            // 0 gaussian, 1 student_t, 2 bernoulli_logit, 3 poisson_log,
                       // 4 neg_binomial_2_log
   int centered;       // 0 non-centred, 1 centred
-  long long M, G;     // observations, groups; D = p + 1 + G
+  long long M, G;     // observations, groups; D = p + 1 + G + learn
   double nu, sigma, prior, tau_scale;
-  // likelihoods 3 and 4: the dispersion (4), and the block's last value, the sum of the
-  // data-only constants; eta0 [M] follows the group offsets in the block
+  // likelihoods 3 and 4: the dispersion (4), and the sum of the data-only constants, the
+  // last value of a fixed block; eta0 [M] follows the group offsets in the block
   double phi, c_data;
+  // learn = 1: the last coordinate is lambda = log sigma (likelihoods 0, 1) or log phi (4),
+  // e^lambda ~ half-Cauchy(0, s_aux); sigma / phi above are not used.  s_aux follows
+  // everything a fixed block has; likelihood 4: J and T [J] follow it (J = 0: no table)
+  int learn;
+  double s_aux;
+  long long J;
 };
+// p, the columns of X, from the dimension of the sample rows (< 1: no such block)
+inline long long mlm_coefs(long long D, const MlmHead& h) { return D - 1 - h.G - h.learn; }
 // log p [n] and (grad non-null) d log p / dx [n][D] of the rows of x [n][D] for the
 // multilevel target whose parameter block is at `params` (device).  scratch holds
 // mlm_scratch_doubles(D, n, h, grad != null) doubles of chunk partials.  grad == nullptr

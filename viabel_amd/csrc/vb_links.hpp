@@ -5,8 +5,12 @@
 //
 // The host part (LinkK, link_has_offset, lgamma_half_step, link_consts) is plain C++ with
 // no HIP runtime call, so a host-only program can include it; the device part (obs_link)
-// is compiled by hipcc only.  The forms with a learned scale or dispersion have one user
-// and stay in vb_glm.hip.
+// is compiled by hipcc only.
+//
+// The forms with a learned scale or dispersion (the last coordinate of a sample row is
+// lambda = log sigma for 0 and 1, log phi for 4) are the kernel instances LIK = 5, 6, 7 of
+// both files: aux_consts on the host; glm_row_consts, glm_link_aux, aux_lambda_prior and
+// disp_row_sums on the device.
 #pragma once
 #include <cmath>
 
@@ -25,6 +29,11 @@ struct LinkK {
 
 // the two count likelihoods add the block's per-observation offset eta0 [M] to eta
 constexpr bool link_has_offset(int lik) { return lik == 3 || lik == 4; }
+
+// the learned instances of the kernels: LIK = 5, 6, 7 are the likelihoods 0, 1, 4 with
+// lambda a coordinate; 7 takes the offset as 4 does
+constexpr bool link_learned(int lik) { return lik >= 5; }
+constexpr bool link_offset(int lik) { return link_has_offset(lik) || lik == 7; }
 
 // lgamma(x + 1/2) - lgamma(x) - log(x) / 2 for x > 0, to a few 2^-53 absolute.  The
 // difference of the two lgamma loses the digits of M c_obs as nu grows (~1e-9 per
@@ -69,6 +78,34 @@ inline double link_consts(int lik, double nu, double sigma, double phi, LinkK* k
   return 0.0;
 }
 
+// log(2 / pi): the half-Cauchy's constant without its scale
+constexpr double kLogTwoOverPi = -0.45158270528945486472619522989488;
+
+// The host constants of a learned block (likelihood 0, 1 or 4; e^lambda ~ half-Cauchy(0,
+// s_aux)): the fixed link's constants at sigma = 1, that is c_obs without -log sigma
+// (-M lambda is the row's) and the student_t's k1, k2; not its k0, k3, which hold sigma,
+// and nothing of the negative binomial's, whose phi and log phi are the row's.  c_aux =
+// log(2 / (pi s_aux)).
+struct AuxConsts {
+  double c_obs, k1, k2, nu, inv_nu, ls_aux, c_aux;
+};
+inline AuxConsts aux_consts(int lik, double nu, double s_aux) {
+  AuxConsts a{};
+  if (lik != 4) {
+    LinkK fixed;
+    a.c_obs = link_consts(lik, nu, 1.0, 0.0, &fixed);
+    a.k1 = fixed.k1;
+    a.k2 = fixed.k2;
+  }
+  if (lik == 1) {
+    a.nu = nu;
+    a.inv_nu = 1.0 / nu;
+  }
+  a.ls_aux = std::log(s_aux);
+  a.c_aux = kLogTwoOverPi - a.ls_aux;
+  return a;
+}
+
 #ifdef __HIPCC__
 // l(y, eta) without its constant, and dl / d eta
 template <int LIK>
@@ -99,6 +136,95 @@ __device__ __forceinline__ void obs_link(const LinkK& k, double eta, double y, d
     l = y * eta - yp * (fmax(z, 0.0) + log1p(e));
     const double inv = 1.0 / (1.0 + e);
     dl = y - yp * (z >= 0.0 ? inv : e * inv);
+  }
+}
+
+// learned mode: a row's link constants from its lambda.  gaussian, student_t: ca =
+// 1 / sigma = exp(-lambda) (the residual is scaled before it is squared, so a residual of
+// exactly 0 stays 0 where sigma^2 leaves the range); neg_binomial: ca = phi, cb = lambda
+template <int LIK>
+__device__ __forceinline__ void glm_row_consts(double lam, double& ca, double& cb) {
+  if constexpr (LIK == 7) {
+    ca = exp(lam);
+    cb = lam;
+  } else {
+    ca = exp(-lam);
+    cb = 0.0;
+  }
+}
+
+// l(y, eta) without its constant and without -lambda, dl / d eta, and the observation's
+// share of dl / d lambda without its -1 (LIK 5: not formed, -M - 2 sum l serves).  K is
+// the kernel's argument block: lk.k1, lk.k2, nu and inv_nu are read (student_t)
+template <int LIK, class K>
+__device__ __forceinline__ void glm_link_aux(const K& k, double ca, double cb, double eta,
+                                             double y, double& l, double& dl, double& dlam) {
+  if constexpr (LIK == 5) {          // q = r / sigma
+    const double q = (y - eta) * ca;
+    l = -0.5 * (q * q);
+    dl = q * ca;
+    dlam = 0.0;
+  } else if constexpr (LIK == 6) {   // t = (nu + 1) q / (nu + q^2): dl = t / sigma, dlam = t q
+    const double q = (y - eta) * ca;
+    const double q2 = q * q;
+    l = -k.lk.k1 * log1p(q2 * k.inv_nu);
+    const double t = k.lk.k2 * q / (k.nu + q2);
+    dl = t * ca;
+    dlam = t * q;
+  } else {                           // phi = ca, zeta = eta - lambda
+    const double z = eta - cb;
+    const double e = exp(-fabs(z));
+    const double yp = y + ca;
+    const double sp = fmax(z, 0.0) + log1p(e);
+    l = y * eta - yp * sp;
+    const double inv = 1.0 / (1.0 + e);
+    const double lg = yp * (z >= 0.0 ? inv : e * inv);
+    dl = y - lg;
+    dlam = lg - ca * sp;             // (y - dl) - phi softplus(zeta)
+  }
+}
+
+// The half-Cauchy prior of e^lambda with its Jacobian, without its constant: sp =
+// softplus(w) and lg = logistic(w) of w = 2 (lambda - log s_aux), from one exp;
+// log p(lambda) = log(2 / (pi s_aux)) - sp + lambda, d / dlambda = 1 - 2 lg
+__device__ __forceinline__ void aux_lambda_prior(double lam, double ls_aux, double& sp, double& lg) {
+  const double w = 2.0 * (lam - ls_aux);
+  const double e = exp(-fabs(w));
+  sp = fmax(w, 0.0) + log1p(e);
+  const double inv = 1.0 / (1.0 + e);
+  lg = w >= 0.0 ? inv : e * inv;
+}
+
+// learned dispersion: A(phi) = sum_{j=1}^{J-1} T_j log1p(j / phi) -> out[row] and
+// dA / dlambda = -sum_j T_j j / (phi + j) -> out[n + row] of the sample row blockIdx.x,
+// whose lambda is x[row * stride + col], phi = exp(lambda) as the row kernels form it.  One
+// 256-thread block per row.  Every term has one sign.  Threads stride over j; the partial
+// sums meet by the wave reduction and then in wave order: the same bits every call.
+__device__ __forceinline__ void disp_row_sums(const double* x, int stride, int col, const double* T,
+                                              long long J, double* out, long long n) {
+  __shared__ double red[8];
+  const long long row = blockIdx.x;
+  const int t = threadIdx.x, w = t >> 6, lane = t & 63;
+  const double phi = exp(x[row * stride + col]);
+  double a = 0.0, da = 0.0;
+  for (long long j = 1 + t; j < J; j += 256) {
+    const double tj = T[j], fj = (double)j;
+    a = fma(tj, log1p(fj / phi), a);
+    da = fma(tj, fj / (phi + fj), da);
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    a += __shfl_xor(a, off, 64);
+    da += __shfl_xor(da, off, 64);
+  }
+  if (lane == 0) {
+    red[w] = a;
+    red[4 + w] = da;
+  }
+  __syncthreads();
+  if (t == 0) {
+    out[row] = ((red[0] + red[1]) + red[2]) + red[3];
+    out[n + row] = -(((red[4] + red[5]) + red[6]) + red[7]);
   }
 }
 #endif  // __HIPCC__

@@ -41,6 +41,20 @@
 // links (poisson_log, neg_binomial_2_log) add the block's offset eta0 [M] to eta.
 // grad == nullptr selects instances without gradient work; the value's operations are
 // the same, so it is the same bit for bit.
+//
+// Learned scale / dispersion (the block's `learn`): the sample rows are [beta (p), u, G
+// more, lambda], D = p + 2 + G, lambda = log sigma (gaussian, student_t) or log phi
+// (neg_binomial_2_log) with e^lambda ~ half-Cauchy(0, s_aux); every other offset stays.
+// The row kernels serve it as the instances LIK = 5, 6, 7 (the learned forms of 0, 1, 4,
+// defined in vb_links.hpp beside the fixed ones): both kernels have one lane per sample
+// row, so a lane forms its row's link constants from x[row][D - 1] in its prologue and
+// keeps them in registers.  dl carries 1 / sigma, so S_g and every formula above hold as
+// written.  sum_m dl/dlambda is one more per-row accumulator (LIK 6, 7 with a gradient;
+// the gaussian's is -M - 2 sum l), stored to the chunk partial pla beside plp.
+// mlm_combine_kernel's learned instances (its second template parameter) add it in the
+// same chunk-order walk, and lane 0 adds -M lambda (gaussian, student_t), the prior of
+// lambda and, for the negative binomial, the table sums A(phi) and dA/dlambda that
+// mlm_disp_kernel formed before the row kernel, and writes grad[row][D - 1].
 #include <algorithm>
 #include <cmath>
 
@@ -78,7 +92,14 @@ struct MlmK {
   double* pl;                     // [n][nchunk]: S of its last group, 0 if the same (grad)
   double* psa;                    // [n][nchunk]: sum S_g at_g of the groups inside (grad)
   double* pg;                     // [nchunk][n][p] (grad)
-  const double* eta0;             // [M]: offset of eta (LIK >= 3; not read otherwise)
+  const double* eta0;             // [M]: offset of eta (LIK 3, 4, 7; not read otherwise)
+  // learned mode (LIK >= 5): column D - 1 of x and grad is lambda
+  long long J;                    // length of T (LIK 7)
+  double nu, inv_nu;              // student_t (lk.k1, lk.k2 as in obs_link)
+  double ls_aux, Mf;              // log s_aux; M as a double
+  const double* T;                // [J]: T[j] = #{m : y_m > j}
+  double* tab;                    // [2][n]: A(phi), dA/dlambda of the rows (LIK 7)
+  double* pla;                    // [n][nchunk]: sum dl/dlambda of the chunk (grad; LIK 6, 7)
 };
 
 // The group g with off[g] <= m < off[g + 1], searched from lo (off[lo] <= m); the
@@ -155,7 +176,8 @@ __device__ __forceinline__ void mlm_store_partials(const MlmK& k, const MlmWalk&
 template <int LIK, bool GRAD, int PP>
 __global__ __launch_bounds__(256) void mlm_rows_lane_kernel(MlmK k) {
   __shared__ double Xs[kMlmTile * PP];
-  constexpr bool OFFS = link_has_offset(LIK);   // eta0 rides behind y in the tile
+  constexpr bool OFFS = link_offset(LIK);       // eta0 rides behind y in the tile
+  constexpr bool LRN = link_learned(LIK);
   __shared__ double ys[OFFS ? 2 * kMlmTile : kMlmTile];
   __shared__ int gs[kMlmTile];
   const int t = threadIdx.x, nt = blockDim.x, p = k.p, G = k.G;
@@ -174,6 +196,8 @@ __global__ __launch_bounds__(256) void mlm_rows_lane_kernel(MlmK k) {
   }
   const double tau = exp_fast(xr[p]);
   const double it = rcp_refined(tau);
+  double ca = 0.0, cb = 0.0, la = 0.0;   // learned mode only
+  if constexpr (LRN) glm_row_consts<LIK>(xr[k.D - 1], ca, cb);
   const int c = blockIdx.y;
   const long long m0 = (long long)c * k.chunk_obs;
   const long long m1 = m0 + k.chunk_obs < k.M ? m0 + k.chunk_obs : k.M;
@@ -207,7 +231,13 @@ __global__ __launch_bounds__(256) void mlm_rows_lane_kernel(MlmK k) {
       for (int d = 0; d < PP; ++d) eta = fma(beta[d], xm[d], eta);
       if constexpr (OFFS) eta += ys[kMlmTile + mm];
       double l, dl;
-      obs_link<LIK>(k.lk, eta, ys[mm], l, dl);
+      if constexpr (LRN) {
+        double dlam;
+        glm_link_aux<LIK>(k, ca, cb, eta, ys[mm], l, dl, dlam);
+        if constexpr (GRAD && LIK != 5) la += dlam;
+      } else {
+        obs_link<LIK>(k.lk, eta, ys[mm], l, dl);
+      }
       lp += l;
       if constexpr (GRAD) {
         w.S += dl;
@@ -220,6 +250,7 @@ __global__ __launch_bounds__(256) void mlm_rows_lane_kernel(MlmK k) {
   mlm_flush<GRAD>(k, w, gfirst, glast, tau, it, gr, live);
   if (!live) return;
   mlm_store_partials<GRAD>(k, w, row, c, lp);
+  if constexpr (GRAD && LRN && LIK != 5) k.pla[row * k.nchunk + c] = la;
   if constexpr (GRAD) {
     double* pg = k.pg + ((long long)c * k.n + row) * p;
 #pragma unroll
@@ -232,7 +263,8 @@ __global__ __launch_bounds__(256) void mlm_rows_lane_kernel(MlmK k) {
 template <int LIK, bool GRAD>
 __global__ __launch_bounds__(64) void mlm_rows_tile_kernel(MlmK k) {
   __shared__ double Xs[kMlmTM * kMlmKS];
-  constexpr bool OFFS = link_has_offset(LIK);   // eta0 rides behind y
+  constexpr bool OFFS = link_offset(LIK);       // eta0 rides behind y
+  constexpr bool LRN = link_learned(LIK);
   __shared__ double ys[OFFS ? 2 * kMlmTM : kMlmTM];
   __shared__ int gs[kMlmTM];
   const int t = threadIdx.x, p = k.p, G = k.G;
@@ -244,6 +276,8 @@ __global__ __launch_bounds__(64) void mlm_rows_tile_kernel(MlmK k) {
   double* gr = GRAD ? k.grad + rr * k.D + p + 1 : nullptr;
   const double tau = exp_fast(xr[p]);
   const double it = rcp_refined(tau);
+  double ca = 0.0, cb = 0.0, la = 0.0;   // learned mode only
+  if constexpr (LRN) glm_row_consts<LIK>(xr[k.D - 1], ca, cb);
   const int c = blockIdx.y;
   const long long m0 = (long long)c * k.chunk_obs;
   const long long m1 = m0 + k.chunk_obs < k.M ? m0 + k.chunk_obs : k.M;
@@ -253,7 +287,7 @@ __global__ __launch_bounds__(64) void mlm_rows_tile_kernel(MlmK k) {
     k.bnd[2 * c] = (double)gfirst;
     k.bnd[2 * c + 1] = (double)glast;
   }
-  double* pg = GRAD ? k.pg + ((long long)c * k.n + rr) * p : nullptr;
+  double* pg =GRAD ? k.pg + ((long long)c * k.n + rr) * p : nullptr;
   MlmWalk w{-1, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   double lp = 0.0;
   int gt = gfirst;
@@ -294,10 +328,17 @@ __global__ __launch_bounds__(64) void mlm_rows_tile_kernel(MlmK k) {
       if (mm < cnt) {
         mlm_enter<GRAD>(k, w, gs[mm], gfirst, glast, tau, it, ar, gr, live);
         double l, dl;
-        if constexpr (OFFS)
+        if constexpr (LRN) {
+          double dlam;
+          glm_link_aux<LIK>(k, ca, cb,
+                            OFFS ? (eta[mm] + w.aeff) + ys[kMlmTM + mm] : eta[mm] + w.aeff, ys[mm],
+                            l, dl, dlam);
+          if constexpr (GRAD && LIK != 5) la += dlam;
+        } else if constexpr (OFFS) {
           obs_link<LIK>(k.lk, (eta[mm] + w.aeff) + ys[kMlmTM + mm], ys[mm], l, dl);
-        else
+        } else {
           obs_link<LIK>(k.lk, eta[mm] + w.aeff, ys[mm], l, dl);
+        }
         lp += l;
         if constexpr (GRAD) {
           w.S += dl;
@@ -323,12 +364,19 @@ __global__ __launch_bounds__(64) void mlm_rows_tile_kernel(MlmK k) {
     }
   }
   mlm_flush<GRAD>(k, w, gfirst, glast, tau, it, gr, live);
-  if (live) mlm_store_partials<GRAD>(k, w, row, c, lp);
+  if (live) {
+    mlm_store_partials<GRAD>(k, w, row, c, lp);
+    if constexpr (GRAD && LRN && LIK != 5) k.pla[row * k.nchunk + c] = la;
+  }
 }
 
 // ---- chunk partials and prior terms: one wave per sample row ---------------------------
-template <bool GRAD>
+// LIK = 0: a fixed block; 5, 6, 7: the learned instances, which also add pla and finish
+// lambda's entry
+template <bool GRAD, int LIK = 0>
 __global__ __launch_bounds__(64) void mlm_combine_kernel(MlmK k) {
+  constexpr bool LRN = link_learned(LIK);
+  constexpr bool LACC = LRN && GRAD && LIK != 5;   // pla is summed
   const int lane = threadIdx.x, p = k.p, G = k.G, nc = k.nchunk;
   const long long row = blockIdx.x;
   const double* xr = k.x + row * k.D;
@@ -363,7 +411,7 @@ __global__ __launch_bounds__(64) void mlm_combine_kernel(MlmK k) {
   ss = wave_sum_dpp(ss);
   // the chunks, 64 at a time: a lane loads one chunk's partials, every lane then walks
   // them in chunk order (the same operations in every lane)
-  double lps = 0.0, sa = 0.0, S = 0.0;
+  double lps = 0.0, sa = 0.0, S = 0.0, las = 0.0;
   int cur = -1;
   auto finish = [&](int g, double Sg) {
     const double a = ar[g];
@@ -379,8 +427,9 @@ __global__ __launch_bounds__(64) void mlm_combine_kernel(MlmK k) {
     const bool ok = cc < nc;
     const long long pr = row * nc + (ok ? cc : nc - 1);
     const double vlp = ok ? k.plp[pr] : 0.0;
-    double vf = 0.0, vl = 0.0, vsa = 0.0;
+    double vf = 0.0, vl = 0.0, vsa = 0.0, vla = 0.0;
     int bf = 0, bl = 0;
+    if constexpr (LACC) vla = ok ? k.pla[pr] : 0.0;
     if constexpr (GRAD) {
       vf = k.pf[pr];
       vl = k.pl[pr];
@@ -391,6 +440,7 @@ __global__ __launch_bounds__(64) void mlm_combine_kernel(MlmK k) {
     const int cnt = nc - cb < 64 ? nc - cb : 64;
     for (int i = 0; i < cnt; ++i) {
       lps += readlane_f64(vlp, i);
+      if constexpr (LACC) las += readlane_f64(vla, i);
       if constexpr (GRAD) {
         sa += readlane_f64(vsa, i);
         const int f = __builtin_amdgcn_readlane(bf, i), l = __builtin_amdgcn_readlane(bl, i);
@@ -419,11 +469,41 @@ __global__ __launch_bounds__(64) void mlm_combine_kernel(MlmK k) {
   const double l1 = w < INFINITY ? log1p_pos_fast(w) : w;
   double cl = u - l1;
   if (k.centered) cl -= (double)G * u;
-  k.logp[row] = k.c_all + (((lps - 0.5 * k.inv_s2 * ss) - 0.5 * zz) + cl);
+  const double v = k.c_all + (((lps - 0.5 * k.inv_s2 * ss) - 0.5 * zz) + cl);
+  if constexpr (LRN) {
+    // -M lambda (gaussian, student_t), the prior of lambda, the table sums (vb_glm.hip's
+    // glm_aux_final, term by term)
+    const double lam = xr[k.D - 1];
+    double sp, lg;
+    aux_lambda_prior(lam, k.ls_aux, sp, lg);
+    const double gp = 1.0 - 2.0 * lg;
+    if constexpr (LIK == 7)
+      k.logp[row] = v + ((lam - sp) + k.tab[row]);
+    else
+      k.logp[row] = v + (fma(-k.Mf, lam, lam) - sp);
+    if constexpr (GRAD) {
+      double gl;
+      if constexpr (LIK == 7)
+        gl = (las + k.tab[k.n + row]) + gp;
+      else if constexpr (LIK == 5)
+        gl = (-2.0 * lps - k.Mf) + gp;
+      else
+        gl = (las - k.Mf) + gp;
+      k.grad[row * k.D + k.D - 1] = gl;
+    }
+  } else {
+    k.logp[row] = v;
+  }
   if constexpr (GRAD) {
     const double gw = w < INFINITY ? fma(-2.0 * w, rcp_refined(1.0 + w), 1.0) : -1.0;
     k.grad[row * k.D + p] = gw + (k.centered ? zz - (double)G : tau * sa);
   }
+}
+
+// learned dispersion: the table sums of the n rows (disp_row_sums of vb_links.hpp), one
+// sample row per block, lambda in the rows' last column
+__global__ __launch_bounds__(256) void mlm_disp_kernel(MlmK k) {
+  disp_row_sums(k.x, k.D, k.D - 1, k.T, k.J, k.tab, k.n);
 }
 
 struct MlmPlan {
@@ -433,12 +513,12 @@ struct MlmPlan {
   long long chunk_obs, row_blocks;
 };
 
-// doubles of chunk partials per chunk
-long long mlm_per_chunk(int p, long long n, bool grad) {
-  return 2 + std::max<long long>(1, n) * (1 + (grad ? 3 + p : 0));
+// doubles of chunk partials per chunk; extra: 1 where a learned block carries pla
+long long mlm_per_chunk(int p, long long n, bool grad, int extra = 0) {
+  return 2 + std::max<long long>(1, n) * (1 + (grad ? 3 + p + extra : 0));
 }
 
-MlmPlan mlm_plan(int p, long long n, long long M, bool grad) {
+MlmPlan mlm_plan(int p, long long n, long long M, bool grad, int extra = 0) {
   MlmPlan pl{};
   pl.small = p <= kMlmLaneP;
   pl.tb = pl.small ? (n <= 4096 ? 64 : 256) : 64;
@@ -446,7 +526,7 @@ MlmPlan mlm_plan(int p, long long n, long long M, bool grad) {
   const long long max_chunks = std::min<long long>((M + kMlmTile - 1) / kMlmTile, 1024);
   long long nc = std::max<long long>(
       1, std::min(max_chunks, (kMlmBlocks + pl.row_blocks - 1) / std::max<long long>(1, pl.row_blocks)));
-  const long long per = mlm_per_chunk(p, n, grad);
+  const long long per = mlm_per_chunk(p, n, grad, extra);
   if (nc > 1 && nc * per > kMlmScratchMax) nc = std::max<long long>(1, kMlmScratchMax / per);
   long long co = (M + nc - 1) / nc;
   co = (co + kMlmTile - 1) / kMlmTile * kMlmTile;
@@ -470,14 +550,36 @@ void mlm_launch(const MlmPlan& pl, const MlmK& k, hipStream_t s) {
     hipLaunchKernelGGL((mlm_rows_lane_kernel<LIK, GRAD, 16>), g, b, 0, s, k);
 }
 
+// the row kernel and the combine kernel of a learned instance
+template <int LIK>
+hipError_t mlm_launch_aux(const MlmPlan& pl, const MlmK& k, hipStream_t s) {
+  const bool g = k.grad != nullptr;
+  g ? mlm_launch<LIK, true>(pl, k, s) : mlm_launch<LIK, false>(pl, k, s);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if (g)
+    hipLaunchKernelGGL((mlm_combine_kernel<true, LIK>), dim3((unsigned)k.n), dim3(64), 0, s, k);
+  else
+    hipLaunchKernelGGL((mlm_combine_kernel<false, LIK>), dim3((unsigned)k.n), dim3(64), 0, s, k);
+  return hipGetLastError();
+}
+
+// a learned block carries pla (the gaussian needs none) and, for a dispersion, tab
+int mlm_extra(const MlmHead& h) { return h.learn && h.lik != 0 ? 1 : 0; }
+size_t mlm_tab_doubles(const MlmHead& h, long long n) {
+  return h.learn && h.lik == 4 ? 2 * (size_t)n : 0;
+}
+
 }  // namespace
 
+// [tab 2 n (learned dispersion)] [bnd] [plp] [pf] [pl] [psa] [pla (learned 1, 4)] [pg]
 size_t mlm_scratch_doubles(int D, long long n, const MlmHead& h, bool grad) {
   if (n < 1) return 0;
-  const int p = D - 1 - (int)h.G;
-  if (p < 1) return 0;
-  const MlmPlan pl = mlm_plan(p, n, h.M, grad);
-  return (size_t)pl.nchunk * (size_t)mlm_per_chunk(p, n, grad);
+  const long long pc = mlm_coefs(D, h);
+  if (pc < 1) return 0;
+  const int p = (int)pc, extra = mlm_extra(h);
+  const MlmPlan pl = mlm_plan(p, n, h.M, grad, extra);
+  return mlm_tab_doubles(h, n) + (size_t)pl.nchunk * (size_t)mlm_per_chunk(p, n, grad, extra);
 }
 
 hipError_t launch_mlm_rows(int D, long long n, const MlmHead& h, const double* params,
@@ -485,10 +587,11 @@ hipError_t launch_mlm_rows(int D, long long n, const MlmHead& h, const double* p
                            hipStream_t s) {
   if (n < 1) return hipSuccess;
   if (!params || !x || !logp || !scratch || h.M < 1 || h.G < 1 || h.G > 0x7fff0000LL ||
-      (long long)D - 1 - h.G < 1)
+      mlm_coefs(D, h) < 1)
     return hipErrorInvalidValue;
-  const int p = D - 1 - (int)h.G;
-  const MlmPlan pl = mlm_plan(p, n, h.M, grad != nullptr);
+  if (h.learn && (h.lik == 2 || h.lik == 3 || h.J < 0 || h.J > 65536)) return hipErrorInvalidValue;
+  const int p = (int)mlm_coefs(D, h), extra = mlm_extra(h);
+  const MlmPlan pl = mlm_plan(p, n, h.M, grad != nullptr, extra);
   if (pl.row_blocks > 0x7fffffffLL || n > 0x7fffffffLL) return hipErrorInvalidValue;
   MlmK k{};
   k.p = p;
@@ -499,28 +602,59 @@ hipError_t launch_mlm_rows(int D, long long n, const MlmHead& h, const double* p
   k.n = n;
   k.M = h.M;
   k.chunk_obs = pl.chunk_obs;
-  const double c_obs = link_consts(h.lik, h.nu, h.sigma, h.phi, &k.lk);
   k.inv_s2 = 1.0 / (h.prior * h.prior);
   k.inv_stau = 1.0 / h.tau_scale;
   // beta's prior, the observations, the half-Cauchy log(2 / (pi s_tau)), the groups' normal
+  double c_obs;
+  if (h.learn) {
+    // as launch_glm_rows forms them for a learned block (vb_links.hpp): c_obs without
+    // -log sigma, and the half-Cauchy log(2 / (pi s_aux)) of e^lambda
+    const AuxConsts a = aux_consts(h.lik, h.nu, h.s_aux);
+    k.lk.k1 = a.k1;
+    k.lk.k2 = a.k2;
+    k.nu = a.nu;
+    k.inv_nu = a.inv_nu;
+    k.ls_aux = a.ls_aux;
+    k.Mf = (double)h.M;
+    c_obs = a.c_obs;
+  } else {
+    c_obs = link_consts(h.lik, h.nu, h.sigma, h.phi, &k.lk);
+  }
   k.c_all = -(double)p * (0.5 * kLog2Pi + std::log(h.prior)) + (double)h.M * c_obs +
             (std::log(2.0 / M_PI) - std::log(h.tau_scale)) - (double)h.G * (0.5 * kLog2Pi);
   if (h.lik >= 3) k.c_all += h.c_data;   // the data-only constants, summed by the packer
+  if (h.learn) k.c_all += kLogTwoOverPi - k.ls_aux;
   k.X = params + kMlmHeader;
   k.y = k.X + (size_t)h.M * p;
   k.off = k.y + h.M;
   k.eta0 = h.lik >= 3 ? k.off + h.G + 1 : nullptr;
+  if (h.learn && h.lik == 4) {   // behind eta0: c_data, s_aux, J
+    k.J = h.J;
+    k.T = k.eta0 + h.M + 3;
+  }
   k.x = x;
   k.logp = logp;
   k.grad = grad;
   const size_t nn = (size_t)n * pl.nchunk;
-  k.bnd = scratch;
-  k.plp = scratch + 2 * (size_t)pl.nchunk;
+  const size_t ntab = mlm_tab_doubles(h, n);
+  if (ntab) k.tab = scratch;
+  k.bnd = scratch + ntab;
+  k.plp = k.bnd + 2 * (size_t)pl.nchunk;
   if (grad) {
     k.pf = k.plp + nn;
     k.pl = k.pf + nn;
     k.psa = k.pl + nn;
-    k.pg = k.psa + nn;
+    k.pla = extra ? k.psa + nn : nullptr;
+    k.pg = k.psa + nn + (extra ? nn : 0);
+  }
+  if (h.learn) {
+    if (h.lik == 4) {
+      hipLaunchKernelGGL(mlm_disp_kernel, dim3((unsigned)n), dim3(256), 0, s, k);
+      hipError_t e = hipGetLastError();
+      if (e != hipSuccess) return e;
+      return mlm_launch_aux<7>(pl, k, s);
+    }
+    return h.lik == 0 ? mlm_launch_aux<5>(pl, k, s) : mlm_launch_aux<6>(pl, k, s);
   }
   const bool g = grad != nullptr;
   if (h.lik == 0)

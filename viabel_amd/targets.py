@@ -503,7 +503,8 @@ MULTILEVEL_HEADER = 8   # doubles before X in a multilevel target's parameter bl
 
 def multilevel_regression(x, y, group, likelihood='gaussian', df=None, scale=1.0,
                           prior_scale=10.0, tau_scale=5.0, centered=False, n_groups=None,
-                          offset=None, phi=None):
+                          offset=None, phi=None, learn_scale=False, learn_phi=False,
+                          hyper_scale=5.0):
     """A regression whose intercept varies by group, evaluated on the device:
       beta_d ~ N(0, prior_scale^2), tau ~ half-Cauchy(0, tau_scale)
       centred       a_g ~ N(0, tau^2),               x = [beta (p), log tau, a (G)]
@@ -517,8 +518,24 @@ def multilevel_regression(x, y, group, likelihood='gaussian', df=None, scale=1.0
     only.  The observations are sorted by group once (a stable sort, the permutation
     kept as `order`) and packed with the group offsets into one parameter array
     (layout in include/viabel_amd.h) that the library uploads per run, so no host call
-    happens inside a fit."""
+    happens inside a fit.
+
+    Learned scale or dispersion, as in `regression`.  learn_scale=True (gaussian, student_t;
+    `scale` is then not used) or learn_phi=True (neg_binomial_2_log; `phi` must then be
+    None) appends one coordinate: x = [beta (p), log tau, G more, lambda], D = p + 2 + G,
+    lambda = log sigma or log phi with e^lambda ~ half-Cauchy(0, hyper_scale) and the
+    Jacobian of the log kept.  Every other coordinate stays where it is.  Such a target
+    carries learned = 'scale' or 'phi'; learn_phi needs max(y) <= 65536."""
     _check_likelihood(likelihood)
+    if learn_scale and likelihood not in ('gaussian', 'student_t'):
+        raise ValueError('learn_scale=True is valid for the gaussian and student_t likelihoods '
+                         'only, not for %r' % (likelihood,))
+    if learn_phi and likelihood != 'neg_binomial_2_log':
+        raise ValueError('learn_phi=True is valid for the neg_binomial_2_log likelihood only, '
+                         'not for %r' % (likelihood,))
+    learn = bool(learn_scale or learn_phi)
+    if learn and not (np.isfinite(hyper_scale) and hyper_scale > 0):
+        raise ValueError('hyper_scale must be positive')
     x, y = _check_design_shape(x, y, '(M, p)')
     m, p = x.shape
     graw = np.asarray(group)
@@ -540,30 +557,60 @@ def multilevel_regression(x, y, group, likelihood='gaussian', df=None, scale=1.0
     n_groups = int(n_groups)
     if int(g.max()) >= n_groups:
         raise ValueError('group label %d is not below n_groups = %d' % (int(g.max()), n_groups))
-    count = _check_design(x, y, likelihood, df, scale, prior_scale, tau_scale=tau_scale)
-    offset = _check_counts(likelihood, y, offset, phi, m)
+    count = _check_design(x, y, likelihood, df, scale, prior_scale, tau_scale=tau_scale,
+                          learn_scale=learn_scale)
+    offset = _check_counts(likelihood, y, offset, phi, m, learn_phi)
+    table = None
+    if learn_phi:
+        if np.any(y > DISPERSION_TABLE_MAX):
+            raise ValueError('learn_phi=True needs max(y) <= %d, got %g: use the fixed-phi target '
+                             '(multilevel_negative_binomial_regression(x, y, group, phi)) for '
+                             'larger counts' % (DISPERSION_TABLE_MAX, float(np.max(y))))
+        table, c_data = dispersion_table(y)
     order = np.argsort(g, kind='stable')
     offsets = np.concatenate([[0], np.cumsum(np.bincount(g, minlength=n_groups))])
     h = MULTILEVEL_HEADER
-    params = np.zeros(h + m * p + m + n_groups + 1 + (m + 1 if count else 0))
-    _fill_link_params(params, likelihood, m, df, phi, scale, prior_scale)
+    # a learned block appends s_aux and, for the dispersion, J and T [J]
+    e = h + m * p + m + n_groups + 1
+    fixed = e + (m + 1 if count else 0)
+    params = np.zeros(fixed + (1 + (1 + table.size if table is not None else 0) if learn else 0))
+    _fill_link_params(params, likelihood, m, df, phi, None if learn_scale else scale, prior_scale)
     params[5] = n_groups
     params[6] = tau_scale
-    params[7] = 1.0 if centered else 0.0
+    params[7] = (1.0 if centered else 0.0) + (2.0 if learn else 0.0)
     params[h:h + m * p] = x[order].ravel()
     params[h + m * p:h + m * p + m] = y[order]
-    e = h + m * p + m + n_groups + 1
     params[h + m * p + m:e] = offsets
     if count:
         params[e:e + m] = offset[order]
-        params[-1] = count_constant(y, phi)
-    t = Target(nat.TARGET_MULTILEVEL, p + 1 + n_groups, 'multilevel_regression', params)
+        params[fixed - 1] = c_data if learn_phi else count_constant(y, phi)
+    if learn:
+        params[fixed] = hyper_scale
+        if learn_phi:
+            params[fixed + 1] = table.size
+            params[fixed + 2:] = table
+    t = Target(nat.TARGET_MULTILEVEL, p + 1 + n_groups + (1 if learn else 0),
+               'multilevel_regression', params)
     t.likelihood = likelihood
     t.n_obs = m
     t.n_groups = n_groups
     t.centered = bool(centered)
     t.order = order
+    if learn:
+        t.n_coef = p
+        t.learned = 'scale' if learn_scale else 'phi'
     return t
+
+
+def multilevel_linear_regression(x, y, group, prior_scale=10.0, tau_scale=5.0, hyper_scale=5.0,
+                                 centered=False, n_groups=None):
+    """The varying-intercept linear model with unknown noise (the radon model): y ~
+    normal(x beta + a_group, sigma), sigma ~ half-Cauchy(0, hyper_scale):
+    multilevel_regression with the gaussian likelihood and learn_scale=True.  The last
+    coordinate is log sigma."""
+    return multilevel_regression(x, y, group, 'gaussian', prior_scale=prior_scale,
+                                 tau_scale=tau_scale, centered=centered, n_groups=n_groups,
+                                 learn_scale=True, hyper_scale=hyper_scale)
 
 
 def multilevel_logistic_regression(x, y, group, prior_scale=10.0, tau_scale=5.0, centered=False,
@@ -575,11 +622,15 @@ def multilevel_logistic_regression(x, y, group, prior_scale=10.0, tau_scale=5.0,
 
 
 def multilevel_robust_regression(x, y, group, df, scale=1.0, prior_scale=10.0, tau_scale=5.0,
-                                 centered=False, n_groups=None):
-    """multilevel_regression with the student_t likelihood."""
+                                 centered=False, n_groups=None, learn_scale=False,
+                                 hyper_scale=5.0):
+    """multilevel_regression with the student_t likelihood.  learn_scale=True: scale ~
+    half-Cauchy(0, hyper_scale) is learned, the last coordinate is log scale and the `scale`
+    argument is not used."""
     return multilevel_regression(x, y, group, 'student_t', df=df, scale=scale,
                                  prior_scale=prior_scale, tau_scale=tau_scale, centered=centered,
-                                 n_groups=n_groups)
+                                 n_groups=n_groups, learn_scale=learn_scale,
+                                 hyper_scale=hyper_scale)
 
 
 def multilevel_poisson_regression(x, y, group, offset=None, prior_scale=10.0, tau_scale=5.0,
@@ -591,12 +642,18 @@ def multilevel_poisson_regression(x, y, group, offset=None, prior_scale=10.0, ta
                                  offset=offset)
 
 
-def multilevel_negative_binomial_regression(x, y, group, phi, offset=None, prior_scale=10.0,
-                                            tau_scale=5.0, centered=False, n_groups=None):
-    """multilevel_regression with the neg_binomial_2_log likelihood."""
+def multilevel_negative_binomial_regression(x, y, group, phi=None, offset=None, prior_scale=10.0,
+                                            tau_scale=5.0, centered=False, n_groups=None,
+                                            learn_phi=False, hyper_scale=5.0):
+    """multilevel_regression with the neg_binomial_2_log likelihood.  learn_phi=True (phi
+    left None): phi ~ half-Cauchy(0, hyper_scale) is learned and the last coordinate is
+    log phi."""
+    if phi is None and not learn_phi:
+        raise TypeError('multilevel_negative_binomial_regression() needs phi, or learn_phi=True')
     return multilevel_regression(x, y, group, 'neg_binomial_2_log', prior_scale=prior_scale,
                                  tau_scale=tau_scale, centered=centered, n_groups=n_groups,
-                                 offset=offset, phi=phi)
+                                 offset=offset, phi=phi, learn_phi=learn_phi,
+                                 hyper_scale=hyper_scale)
 
 
 def callback(logdensity_and_grad, dim=None, name='callback'):
